@@ -1,19 +1,25 @@
 #!/usr/bin/env python3
 """bench.py — pod-placement decisions/s of the scheduling-cycle core on synthetic cluster snapshots.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config C5 --scale 1.0]
+    python bench.py --gpus 1 --steps K --warmup W [--config C5 --scale 1.0] [--dump-outputs DIR] [--full]
 
 A "step" is one scheduling cycle of the hot path over one snapshot that is already resident in HBM:
 kai_session_reset (the OnSessionOpen math: node accounting, proportion totals / usage / fair-share) followed by
 the allocate Action.  The unit of work is one placement decision = one allocateTask (scores every node of the node
 set, picks the best fitting one, ends in allocate / pipeline / fail — SURVEY.md section 8d).
 
-Prints ONE JSON line with the contract's fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the contract's fields plus the workload,
+the engine's counters of the timed steps and
   roofline     — the dominant kernel against the resource it saturates: on the batch path the fill kernel against instruction issue of its working wavefronts (with the decision
                  throughput against HBM — algorithmic bytes = decisions x (N x 128 B + 80 B), SURVEY 8d — beside it as `algorithmic_vs_streaming`); on the sequential engine k_action
                  against HBM
   cpu_baseline — the CPU oracle (a faithful single-thread restatement of the reference path, kind "port") timed on a
-                 bounded sample of the same workload on this box's host cores.
+                 bounded sample of the same workload on the host's cores (--full).
+
+--full adds what takes runs or checks of its own: the operations' hash against the oracle's pin (parity_full), the CPU baselines,
+the per-cycle session-open legs, the replicas leg of a node-sharded run and the other BASELINE shapes (other_shapes).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): its operations per action
+(ops_<action>.npy: kind, pod, node, job), the pods' states (pod_status.npy, pod_node.npy) and the queues' shares (queue_<field>.npy).
 """
 from __future__ import annotations
 
@@ -32,6 +38,22 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 B_NODE, B_POD_OUT = 128, 80  # algorithmic bytes per node of the node set / per decision
 
 CONFIGS = {"C1": 0, "C2": 1, "C3": 2, "C4": 3, "C5": 4}
+DUMP_BYTES = 60 << 20        # --dump-outputs writes at most this much (64 MB with room for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  Above DUMP_BYTES in all, each array of more than 1 MiB keeps a fixed, seeded sample
+    of its rows (the same rows for the same length), so that two builds with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+    big = sum(a.nbytes for a in arrays.values()) - small
+    for name, a in arrays.items():
+        if small + big > DUMP_BYTES and a.nbytes > 1 << 20:
+            keep = max(1, a.shape[0] * (DUMP_BYTES - small) // big)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_traffic(workload, kernel):
@@ -56,7 +78,9 @@ def main():
     ap.add_argument("--mixed", action="store_true", help="config C5 in the shape SURVEY 8d gives it: zone/rack labels, 5 %% topology gangs, 5 %% elastic gangs, minruntime — jobs the batch path leaves to the sequential engine")
     ap.add_argument("--fractions", type=float, default=0.0, help="that share of the one-GPU pods asks for a fraction of one device (shared GPUs: every decision is a brute-force scan of the nodes' GPU groups — the streaming kernel of SURVEY 8d)")
     ap.add_argument("--queue-depth", type=int, default=0, help="queueDepthPerAction for reclaim / preempt / consolidation (jobs tried per queue and action; 0 = the default: unlimited).  The reference's operator docs configure 5 .. 15 (docs/operator/README.md:64-66, scheduling-shards.md:51-54)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="decisions the CPU oracle is timed on (-1 = auto, 0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="decisions the CPU oracle is timed on (-1 = auto, 0 = skip; --full only)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the oracle hash check, the CPU baselines, the session-open legs, the replicas leg and the other BASELINE shapes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
 
     # `--gpus N` launched plainly (no WORLD_SIZE): one rank per GPU is the contract, so the script starts itself under torch.distributed.run — a line that says
@@ -174,9 +198,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = pkg.dist.max_over_ranks(elapsed, device=red_dev)
+    if args.dump_outputs and rank == 0:  # the last timed step: its operations as the caller received them, then the session state it left
+        dumped = {f"ops_{a}": np.stack([o["kind"], o["pod"], o["node"], o["job"]], 1) for a, o in zip(actions, first_ops)}
+        dumped["pod_status"], dumped["pod_node"] = ssn.pod_states()
+        dumped.update({f"queue_{k}": v for k, v in ssn.queue_shares().items()})
+        dump_outputs(args.dump_outputs, dumped)
     ssn.close(); core.destroy()
 
-    first_ops = [(int(x["kind"]), int(x["pod"]), int(x["node"]), int(x["job"])) for o in first_ops for x in o]  # the last step's committed operations
+    first_ops = [(int(x["kind"]), int(x["pod"]), int(x["node"]), int(x["job"])) for o in first_ops for x in o] if args.full else []  # the last step's committed operations
     if sharded:  # one job: every rank committed the same operations
         total_decisions, total_placed = decisions * args.steps, placed * args.steps
     else:        # replicas: one scheduling shard per rank
@@ -283,7 +312,7 @@ def main():
         "roofline": roof,
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # end-to-end pin: SHA-256 of this run's committed operations against the oracle's full-size run of the same workload (tools/pin_full_sizes.py wrote
         # profiles/full_size_pins.json on the CPU: oracle vs host-compiled engine, every operation / pod / node / share equal)
         import kai_testlib as T
@@ -295,7 +324,7 @@ def main():
             pin = None
         out["parity_full"] = {"ops": len(first_ops), "ops_sha256": sha, "oracle_ops_sha256": pin["ops_sha256"] if pin else None, "equal_to_oracle": (sha == pin["ops_sha256"]) if pin else None,
                               "oracle_pin": "profiles/full_size_pins.json (oracle end to end on the CPU, %s s)" % pin["oracle_s"] if pin else "no pin on file for this workload"}
-    if rank == 0 and world == 1 and args.cpu_sample != 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample != 0:
         import kai_testlib as T
         # (1) contract baseline: the oracle (faithful single-thread restatement of the reference path) on a bounded sample of the SAME snapshot:
         #     it walks the same fair order and stops after `sample` decisions; its operations must be the first operations of the GPU's
@@ -358,7 +387,7 @@ def main():
                 out["cpu_same_algorithm"] = same
             except Exception as e:
                 out["cpu_same_algorithm"] = {"error": str(e)[:200]}
-    if rank == 0 and world == 1 and os.environ.get("KAI_BENCH_OPEN_LEG", "1" if elapsed / args.steps < 5.0 else "0") != "0":  # (not for cycles of many seconds: the leg repeats the cycle several times)
+    if rank == 0 and world == 1 and args.full and os.environ.get("KAI_BENCH_OPEN_LEG", "1" if elapsed / args.steps < 5.0 else "0") != "0":  # (not for cycles of many seconds: the leg repeats the cycle several times)
         # What a production scheduler pays per cycle: every cycle opens a session on a NEW snapshot (scheduler.go:112-138, framework/framework.go:32-65), so
         # kai_session_open — host preparation (node permutation, task / job orders, scan classes: on the host's cores), ~80 MB over PCIe, the OnSessionOpen
         # kernels — belongs to the cycle.  `value` above keeps the contract's definition (inputs resident in HBM); these two legs are reported beside it:
@@ -403,7 +432,7 @@ def main():
             out["config"]["p50_cycle_latency_ms_note"] = "reset of the HBM-resident snapshot + actions; with the per-cycle open: cycle_with_open_ms"
         except Exception as e:  # additional evidence
             out["cycle_with_open_ms"] = {"error": str(e)[:200]}
-    if sharded and os.environ.get("KAI_BENCH_REPLICAS_LEG", "1") != "0":
+    if sharded and args.full and os.environ.get("KAI_BENCH_REPLICAS_LEG", "1") != "0":
         try:
             # second leg, every rank: the same GPUs as independent scheduling shards (how KAI itself scales out: one scheduler instance per node pool,
             # conf/scheduler_conf.go:95-112) — one snapshot of the same shape per rank, no data-path collective, same bracket; reported beside the sharded value
@@ -430,7 +459,7 @@ def main():
                                "note": f"{world} independent scheduling shards of the same shape, one per GPU, no data-path collective (the default for N > 1)"}
         except Exception as e:  # the second leg is additional evidence: it must not take the sharded result down with it (every rank runs the same code, so a failure is common to all)
             out["replicas"] = {"error": str(e)[:200]}
-    if rank == 0 and world == 1 and args.config == "C5" and args.scale == 1.0 and not args.mixed and args.fractions == 0 and actions == ("allocate",) and os.environ.get("KAI_BENCH_OTHER_SHAPES", "1") != "0":
+    if rank == 0 and world == 1 and args.full and args.config == "C5" and args.scale == 1.0 and not args.mixed and args.fractions == 0 and actions == ("allocate",) and os.environ.get("KAI_BENCH_OTHER_SHAPES", "1") != "0":
         # beside the headline (plain gangs: every job on the batch path): the same cluster in the shape SURVEY 8d writes down — zone / rack labels, 5 % of the gangs with a
         # required rack, 5 % elastic, minruntime on — and config 3 with 30 % of its one-GPU pods as fractions of a device; both run on the sequential engine with its passes
         # over the nodes on the scan grid.  One warm-up + one timed cycle each; additional evidence, never part of `value`.

@@ -1,5 +1,5 @@
 """BASELINE config 4 at a given scale with queueDepthPerAction for the victim actions: the ORACLE end to end (8 threads) against the host-compiled engine, operations hashed
-into profiles/full_size_pins.json (what bench.py's parity_full compares the MI355X's run with).  usage: pin_c4_depth.py <scale> <depth> [--no-oracle]"""
+into profiles/full_size_pins.json (what bench.py --full's parity_full compares the MI355X's run with).  usage: pin_c4_depth.py <scale> <depth> [--no-oracle]"""
 import sys, os, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)

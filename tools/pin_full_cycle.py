@@ -11,7 +11,7 @@ acts = ("allocate", "consolidation", "reclaim", "preempt")
 snap, cfg, desc = T.pkg.synth.config(4, scale)
 for a in ("consolidation", "reclaim", "preempt"):
     cfg.queue_depth[T.abi.ACTIONS[a]] = depth
-desc += f", queueDepthPerAction {depth} for the victim actions"  # (the string bench.py builds for --queue-depth: its parity_full looks the pin up by workload + actions)
+desc += f", queueDepthPerAction {depth} for the victim actions"  # (the string bench.py builds for --queue-depth: its parity_full, with --full, looks the pin up by workload + actions)
 t = time.time(); r = HostSim.run(snap, cfg, acts); th = time.time() - t
 t = time.time(); o = T.Oracle.run(snap, cfg, acts, threads=8); to = time.time() - t
 sha, osha = T.ops_sha256(r.ops), T.ops_sha256(o.ops)

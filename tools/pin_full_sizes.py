@@ -1,7 +1,7 @@
 """Pins the benched sizes against the oracle END TO END on the CPU: BASELINE config 3 and config 5 at full size, the oracle
 (node scoring on 8 threads, same results as one thread: tests/test_oracle_threads.py) against the host-compiled engine (tests/host_sim = the
 device engine's source under g++) — every committed operation, pod state, node and queue share — and writes the SHA-256 of the operation
-stream to profiles/full_size_pins.json.  bench.py prints the same hash of the MI355X's operations (`ops_sha256`) and compares it with this file.
+stream to profiles/full_size_pins.json.  bench.py --full prints the same hash of the MI355X's operations (`ops_sha256`) and compares it with this file.
 
     python tools/pin_full_sizes.py C3 C5        (C5: about 10-20 minutes of oracle time on 8 cores)
 """
