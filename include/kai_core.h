@@ -379,6 +379,42 @@ int kai_session_open(kai_core* core, const kai_snapshot_soa* snap);
  * kai_session_open.  Lets a caller replay scheduling cycles on one snapshot (benchmarks, what-if runs). */
 int kai_session_reset(kai_core* core);
 
+/* A pod and node delta applied to the open session's snapshot: what changes between two scheduling cycles of a live cluster (the pods the last cycle placed go
+ * Binding -> Running, pipelined / evicted ones go back to Pending or Releasing, a few finish or are deleted, a few nodes are cordoned, go NotReady or change
+ * allocatable).  Indices are the snapshot's (the caller's order); NULL optional arrays leave that quantity unchanged.
+ *
+ * Contract.  Let S be the snapshot of the last kai_session_open or kai_session_update and S' be S with the delta applied.  After KAI_OK the handle is
+ * indistinguishable from one that has just run kai_session_open(S'): the same kai_queue_shares, kai_node_states, kai_pod_states and kai_pod_gpu_groups, bit for
+ * bit, and the same operations, states, shares, groups and decision counters from every action run afterwards (the batch path or the sequential engine included,
+ * kai_action_stats.reserved[4]).  The update applies to the snapshot, not to the state the actions left: it discards their results as kai_session_reset does,
+ * and kai_session_reset afterwards returns to S'.
+ *  - KAI_ERR_INVALID_ARG: a wrong version, an index out of range (a pod, a node, a pod_node other than -1 .. n_nodes-1), a pod or node listed twice,
+ *    a NULL required array with a count above 0;
+ *  - KAI_ERR_STATE: no open session;
+ *  - KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1); a delta kai_session_open(S') would refuse (e.g. a KAI_POD_GPU_UNMODELLED pod made active,
+ *    a KAI_POD_CPU_FALLBACK pod made pending, a node that gains GPUs with another node_gpu_memory in a session with shared-GPU requests), with the open's
+ *    status; and, in such a session, a delta after which every node that has GPUs is a new one with another memory size, or none is left while the caller's
+ *    node 0 has another one (the cluster's GPU memory size would change, and every fraction's memory with it: open S').
+ *  Every refusal is decided before the first write and leaves the session exactly as it was (still open, same snapshot, same state); only a HIP failure after
+ *  the writes began closes it, as a failed open does.  The host work is proportional to the delta (plus, in a session with shared-GPU requests, one pass over
+ *  the nodes' lists of active pods); the session math is re-derived on the device as kai_session_reset does.
+ *  Anything the delta cannot express needs a full open: pods, jobs, pod-sets, queues or nodes added or removed; requests, classes, class_fit, topologies,
+ *  queue quotas or the config changed. */
+#define KAI_DELTA_VERSION 1u
+typedef struct kai_session_delta {
+    uint32_t version;                /* KAI_DELTA_VERSION */
+    int32_t n_pods;                  /* pods whose state changed */
+    const int32_t* pod;              /* [n_pods] pod index in the snapshot's (caller's) order */
+    const int32_t* pod_status;       /* [n_pods] new kai_pod_status */
+    const int32_t* pod_node;         /* [n_pods] new node index (caller's order) or -1 */
+    const int32_t* pod_gpu_group;    /* [n_pods] new shared-GPU group id or -1; NULL = unchanged */
+    int32_t n_nodes;                 /* nodes whose state changed */
+    const int32_t* node;             /* [n_nodes] node index (caller's order) */
+    const uint32_t* node_flags;      /* [n_nodes] new KAI_NODE_* bits; NULL = unchanged */
+    const double* node_allocatable;  /* [R][n_nodes] new status.allocatable; NULL = unchanged */
+} kai_session_delta;
+int kai_session_update(kai_core* core, const kai_session_delta* delta);
+
 /* replaces: ssn.QueueFairShare / QueueAllocatedResources / QueueDeservedResources
  * (plugins/proportion/proportion.go:508-521) */
 int kai_queue_shares(kai_core* core, kai_queue_share* out, int cap);

@@ -109,6 +109,53 @@ class KaiSnapshotSoA(C.Structure):
     ]
 
 
+DELTA_VERSION = 1  # KAI_DELTA_VERSION
+
+
+class KaiSessionDelta(C.Structure):
+    """kai_session_delta (include/kai_core.h): pod and node changes applied to the open session by kai_session_update."""
+    _fields_ = [("version", C.c_uint32), ("n_pods", C.c_int32), ("pod", C.POINTER(C.c_int32)), ("pod_status", C.POINTER(C.c_int32)),
+                ("pod_node", C.POINTER(C.c_int32)), ("pod_gpu_group", C.POINTER(C.c_int32)), ("n_nodes", C.c_int32), ("node", C.POINTER(C.c_int32)),
+                ("node_flags", C.POINTER(C.c_uint32)), ("node_allocatable", C.POINTER(C.c_double))]
+
+
+def apply_delta(snap: "Snapshot", pods, status, node, gpu_group=None, nodes=None, node_flags=None, node_allocatable=None) -> "Snapshot":
+    """S' = S with a kai_session_delta applied: a new Snapshot (arrays the delta touches are copied, the others shared) that kai_session_open accepts.
+    node_allocatable is [R][len(nodes)], as in the C struct."""
+    a = dict(snap.arrays)
+    pods = np.asarray(pods, np.int64)
+    if len(pods):
+        a["pod_status"] = a["pod_status"].copy(); a["pod_status"][pods] = np.asarray(status, np.int32)
+        a["pod_node"] = a["pod_node"].copy(); a["pod_node"][pods] = np.asarray(node, np.int32)
+        if gpu_group is not None:
+            g = a["pod_gpu_group"].copy() if "pod_gpu_group" in a else np.full(snap.n_pods, -1, np.int32)
+            g[pods] = np.asarray(gpu_group, np.int32); a["pod_gpu_group"] = g
+    if nodes is not None and len(nodes):
+        nodes = np.asarray(nodes, np.int64)
+        if node_flags is not None:
+            a["node_flags"] = a["node_flags"].copy(); a["node_flags"][nodes] = np.asarray(node_flags, np.uint32)
+        if node_allocatable is not None:
+            a["node_allocatable"] = a["node_allocatable"].copy(); a["node_allocatable"][:, nodes] = np.asarray(node_allocatable, np.float64).reshape(snap.n_res, len(nodes))
+    out = Snapshot(n_res=snap.n_res, arrays=a, node_names=snap.node_names, pod_names=snap.pod_names, job_names=snap.job_names,
+                   queue_names=snap.queue_names, podset_names=snap.podset_names)
+    out.finalize()
+    return out
+
+
+def next_cycle_delta(snap: "Snapshot", ops, rng, succeeded_frac=0.01) -> dict:
+    """The delta a real next cycle carries after a cycle's operations `ops` (kai_op records): the allocated pods Running at their nodes, the pipelined ones
+    Pending, and `succeeded_frac` of the running pods Succeeded.  Keyword arguments of apply_delta / Session.update (pods, status, node)."""
+    placed = {int(o["pod"]): int(o["node"]) for o in ops if int(o["kind"]) == 0}
+    piped = [int(o["pod"]) for o in ops if int(o["kind"]) == 1 and int(o["pod"]) not in placed]
+    running = np.nonzero(snap.pod_status == 1 << 6)[0]
+    k = int(len(running) * succeeded_frac)
+    done = [int(p) for p in rng.choice(running, size=k, replace=False) if int(p) not in placed] if k else []
+    pods = list(placed) + piped + done
+    status = [1 << 6] * len(placed) + [1] * len(piped) + [1 << 8] * len(done)
+    node = list(placed.values()) + [-1] * (len(piped) + len(done))
+    return dict(pods=pods, status=status, node=node)
+
+
 class KaiOp(C.Structure):
     _fields_ = [("seq", C.c_int64), ("kind", C.c_int32), ("pod", C.c_int32), ("node", C.c_int32), ("job", C.c_int32), ("stmt", C.c_int32), ("pad", C.c_int32)]
 

@@ -22,10 +22,27 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
 EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node",
-           "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_close", "kai_last_error", "kai_version"]
+           "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_close", "kai_last_error", "kai_version"]
 
 
 _OP_DTYPE = np.dtype([("seq", "<i8"), ("kind", "<i4"), ("pod", "<i4"), ("node", "<i4"), ("job", "<i4"), ("stmt", "<i4"), ("pad", "<i4")])  # kai_op (include/kai_core.h)
+
+
+def delta_struct(pods, status, node, gpu_group=None, nodes=None, node_flags=None, node_allocatable=None, version=abi.DELTA_VERSION):
+    """A kai_session_delta and the numpy arrays it points into (keep them alive while the struct is in use); None = a NULL array."""
+    def arr(x, dt):
+        return None if x is None else np.ascontiguousarray(x, dtype=dt)
+    keep = [arr(pods, np.int32), arr(status, np.int32), arr(node, np.int32), arr(gpu_group, np.int32), arr(nodes, np.int32), arr(node_flags, np.uint32),
+            arr(node_allocatable, np.float64)]
+    def ptr(x, ct):
+        return None if x is None else x.ctypes.data_as(C.POINTER(ct))
+    d = abi.KaiSessionDelta()
+    d.version = version
+    d.n_pods = 0 if keep[0] is None else len(keep[0])
+    d.pod, d.pod_status, d.pod_node, d.pod_gpu_group = ptr(keep[0], C.c_int32), ptr(keep[1], C.c_int32), ptr(keep[2], C.c_int32), ptr(keep[3], C.c_int32)
+    d.n_nodes = 0 if keep[4] is None else len(keep[4])
+    d.node, d.node_flags, d.node_allocatable = ptr(keep[4], C.c_int32), ptr(keep[5], C.c_uint32), ptr(keep[6], C.c_double)
+    return d, keep
 
 
 class KaiError(RuntimeError):
@@ -74,6 +91,7 @@ def load_library(path: str = LIB_PATH):
     lib.kai_shard_allgather_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.kai_pod_gpu_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
     lib.kai_session_reset.argtypes = [C.c_void_p]
+    lib.kai_session_update.argtypes = [C.c_void_p, C.POINTER(abi.KaiSessionDelta)]
     lib.kai_queue_shares.argtypes = [C.c_void_p, C.POINTER(abi.KaiQueueShare), C.c_int]
     lib.kai_action_execute.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64)]
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
@@ -281,6 +299,14 @@ class Session:
     def reset(self):
         """Re-open the session from the HBM-resident snapshot (no host traffic)."""
         self.core._check(self.core.lib.kai_session_reset(self.core.handle))
+
+    def update(self, pods, status, node, gpu_group=None, nodes=None, node_flags=None, node_allocatable=None):
+        """kai_session_update: apply a pod / node delta to the session's snapshot (the handle then equals one that opened S'; include/kai_core.h).
+        pods / status / node: the changed pods, their new status and node (caller's index or -1); gpu_group: their new shared-GPU groups (None = unchanged);
+        nodes: the changed nodes, with node_flags ([n]) and / or node_allocatable ([R][n]), None = unchanged.  On success self.snap becomes S'."""
+        d, _keep = delta_struct(pods, status, node, gpu_group, nodes, node_flags, node_allocatable)
+        self.core._check(self.core.lib.kai_session_update(self.core.handle, C.byref(d)))
+        self.snap = abi.apply_delta(self.snap, pods, status, node, gpu_group, nodes, node_flags, node_allocatable)
 
     def close(self):
         self.core.lib.kai_session_close(self.core.handle)

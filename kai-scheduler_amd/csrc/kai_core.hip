@@ -21,6 +21,8 @@
 #include "kai_batch_kernels.hpp"
 #include "kai_batch_driver.hpp"
 #include "kai_victim_shard.hpp"
+#include "kai_delta.hpp"
+#include <map>
 #include <thread>
 
 using namespace kai;
@@ -78,6 +80,18 @@ struct kai_core {
     HostPrep prep; SharedPods sp;
     // pinned host staging for the snapshot's own arrays (kai_session_open, UploadStage): grows, lives with the handle
     void* up_pin = nullptr; size_t up_pin_bytes = 0;
+    // kai_session_update (kai_delta.hpp): what the open derives from pod status / node / group and node flags / allocatable, kept so that a delta adjusts it
+    // (HostPrep keeps the class operands, the exact-sum counts and the nodes' rows in engine order)
+    bool idx_forced_off = false, fast_forced_off = false;  // the open's shared-GPU / MIG rules on the class index and the staged job path
+    bool legacy_on = false; std::vector<int32_t> legacy_cnt;  // per engine node: active legacy MIG tasks (only when the snapshot has such a pod)
+    bool gm_guard = false;  // shared-GPU requests + node_gpu_memory: the cluster's one GPU memory size is found among the nodes that have GPUs
+    std::vector<int64_t> h_gpu_mem;  // node_gpu_memory in engine order (what n_gpu_mem holds)
+    std::map<int32_t, int32_t> new_groups;  // shared-GPU group ids >= KAI_NEW_GROUP in the snapshot and how many pods carry them (next_group0)
+    std::vector<std::vector<std::pair<uint32_t, int32_t>>> np_lists; std::vector<uint32_t> np_uid; size_t np_cap = 0;  // shared GPUs: each node's active pods as (UID rank, pod); every pod's UID rank
+    decltype(KaiCtx::bt) bt_pools{}; bool bt_alloc = false; int bt_C = 0;  // the batch path's pools of this session (bound for bt_C classes)
+    int cls_cap = 0;  // classes the session's cls / sum1_key / sum1_node arrays hold
+    uint32_t* d_rank = nullptr; int32_t* d_pkey = nullptr; int32_t* d_remap = nullptr; size_t remap_cap = 0;  // first update of a session: name ranks, pods' request keys, key -> class
+    unsigned char* dl_pin = nullptr; size_t dl_pin_bytes = 0; unsigned char* dl_dev = nullptr; size_t dl_dev_bytes = 0;  // the delta's staging: pinned and device, grows, lives with the handle
 };
 
 #define HIP_TRY(core, expr)                                                                                        \
@@ -229,6 +243,7 @@ void free_session(kai_core* core, bool release = false) {
     for (size_t i = 0; i < core->bufs.size(); i++) core->spare.push_back({core->bufs[i], core->buf_bytes[i]});
     core->bufs.clear(); core->buf_bytes.clear(); core->slab = nullptr; core->slab_left = 0;
     if (release) { for (auto& sp : core->spare) (void)hipFree(sp.first); core->spare.clear(); if (core->rep_buf) (void)hipFree(core->rep_buf); core->rep_buf = nullptr; core->rep_buf_bytes = 0; }
+    core->d_rank = nullptr; core->d_pkey = nullptr; core->d_remap = nullptr; core->remap_cap = 0; core->bt_alloc = false;
     core->allocs.clear(); core->sv_base = nullptr; core->xr_base = nullptr; core->mw_world = 0; core->rep_mem = nullptr; core->d_ctxs = nullptr; core->d_mw = nullptr; core->d_segs = nullptr; core->d_sg = nullptr;
     core->open = false;
 }
@@ -547,6 +562,8 @@ int kai_core_destroy(kai_core* core) {
     if (!core) return KAI_ERR_INVALID_ARG;
     (void)hipSetDevice(core->device);
     free_session(core, true);
+    if (core->dl_pin) { (void)hipHostFree(core->dl_pin); core->dl_pin = nullptr; }
+    if (core->dl_dev) { (void)hipFree(core->dl_dev); core->dl_dev = nullptr; }
     if (core->pin_buf) { (void)hipHostFree(core->pin_buf); core->pin_buf = nullptr; core->pin_bytes = 0; }
     if (core->up_pin) { (void)hipStreamSynchronize(core->stream); (void)hipHostFree(core->up_pin); core->up_pin = nullptr; core->up_pin_bytes = 0; }
     if (core->rccl_comm) { (void)hipStreamSynchronize(core->stream); if (RcclApi* a = rccl_api()) (void)a->CommDestroy(core->rccl_comm); core->rccl_comm = nullptr; }
@@ -644,8 +661,9 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     catch (const std::bad_alloc&) { throw; }  // (a worker thread's included: kai_parallel.hpp carries it here)
     catch (const std::exception& e) { core->err = std::string("host preparation: ") + e.what(); return KAI_ERR_INVALID_ARG; }
     const auto t_prep = tnow();
-    if (any_legacy_mig) for (int p = 0; p < P; p++)  // NodeInfo.LegacyMIGTasks (node_info.go:407-409): a node that holds a legacy MIG task takes no MIG request
-        if ((s->pod_flags[p] & KAI_POD_LEGACY_MIG) && prep.pod_node[p] >= 0 && (s->pod_status[p] & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING))) prep.node_flags[prep.pod_node[p]] |= KAI_NODE_LEGACY_MIG_I;
+    core->legacy_on = any_legacy_mig; core->legacy_cnt.clear();
+    if (any_legacy_mig) { core->legacy_cnt.assign((size_t)N, 0); for (int p = 0; p < P; p++)  // NodeInfo.LegacyMIGTasks (node_info.go:407-409): a node that holds a legacy MIG task takes no MIG request
+        if ((s->pod_flags[p] & KAI_POD_LEGACY_MIG) && prep.pod_node[p] >= 0 && (s->pod_status[p] & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING))) { prep.node_flags[prep.pod_node[p]] |= KAI_NODE_LEGACY_MIG_I; core->legacy_cnt[(size_t)prep.pod_node[p]]++; } }
     core->perm = prep.perm;
 
     int rc;
@@ -691,7 +709,7 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     if (s->queue_preempt_min_runtime_ns) TRY(dupload_f(core, c.q_preempt_mr, s->queue_preempt_min_runtime_ns, (size_t)Q));
     if (s->queue_reclaim_min_runtime_ns) TRY(dupload_f(core, c.q_reclaim_mr, s->queue_reclaim_min_runtime_ns, (size_t)Q));
     c.now_ns = core->cfg.now_ns; c.def_preempt_mr = core->cfg.default_preempt_min_runtime_ns; c.def_reclaim_mr = core->cfg.default_reclaim_min_runtime_ns; c.reclaim_method = core->cfg.reclaim_resolve_method;
-    TRY(dupload_f(core, c.cls, prep.classes.data(), prep.classes.size()));
+    TRY(dupload_f(core, c.cls, prep.classes.data(), prep.classes.size())); core->cls_cap = std::max(c.C, 1);
     TRY(dzero_f(core, c.sum1_key, (size_t)std::max(c.C, 1) * std::max(c.NB, 1))); TRY(dzero_f(core, c.sum1_node, (size_t)std::max(c.C, 1) * std::max(c.NB, 1)));
 
     // ---- shared GPUs: per-pod portion / group, per-node GPU memory and group tables (api/node_info/gpu_sharing_node_info.go)
@@ -718,7 +736,8 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
         std::vector<double> por; std::vector<int32_t> grp, minus1;
         if (!lean_pods) {
             por.assign(P1, 0.0); grp.assign(P1, -1); minus1.assign(P1, -1);
-            for (int p = 0; p < P; p++) { por[p] = s->pod_gpu_portion ? s->pod_gpu_portion[p] : 0.0; grp[p] = (s->pod_gpu_group && sp.shared[p]) ? s->pod_gpu_group[p] : -1; if (grp[p] >= next_new) next_new = grp[p] + 1; }
+            core->new_groups.clear();
+            for (int p = 0; p < P; p++) { por[p] = s->pod_gpu_portion ? s->pod_gpu_portion[p] : 0.0; grp[p] = (s->pod_gpu_group && sp.shared[p]) ? s->pod_gpu_group[p] : -1; if (grp[p] >= next_new) next_new = grp[p] + 1; if (grp[p] >= KAI_NEW_GROUP) core->new_groups[grp[p]]++; }
         }
         auto ones = [&](auto& field, size_t n) -> int { int rc2 = dalloc_f(core, field, n); if (rc2) return rc2; HIP_TRY(core, hipMemsetAsync(KAI_VP(field), 0xFF, std::max<size_t>(n, 1) * sizeof(*field), core->stream)); return KAI_OK; };  // -1 in every element
         auto gpu_row = [&](auto& field) -> int {  // the pods' GPU requests: a device-to-device copy of that row of p_req
@@ -746,7 +765,10 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
         c.shared_on = shared ? 1 : 0;
         // shared GPUs: the pods that ask for a fraction are in no class (brute-force scans over the nodes' GPU groups), the other classes stay indexed with the gpusharingorder bit in their
         // keys (kai_engine.hpp key_shared_layout; KAI_SHARED_INDEX=0: every scan by brute force, as before round 6); MIG rows: every scan by brute force (the class keys do not know the MIG predicates)
-        if (shared || sp.mig) { c.all_tracked = 0; const char* e = std::getenv("KAI_SHARED_INDEX"); const int lvl = e ? std::atoi(e) : 2; if (sp.mig || lvl == 0) c.use_index = 0; if (sp.mig || lvl < 2) { c.fast_ok = 0; core->fast_ok0 = 0; } }  // (2: gangs without a fraction pod also keep the staged job path)
+        core->idx_forced_off = false; core->fast_forced_off = false;
+        if (shared || sp.mig) { c.all_tracked = 0; const char* e = std::getenv("KAI_SHARED_INDEX"); const int lvl = e ? std::atoi(e) : 2; if (sp.mig || lvl == 0) { c.use_index = 0; core->idx_forced_off = true; } if (sp.mig || lvl < 2) { c.fast_ok = 0; core->fast_ok0 = 0; core->fast_forced_off = true; } }  // (2: gangs without a fraction pod also keep the staged job path)
+        core->gm_guard = shared && s->node_gpu_memory != nullptr;
+        core->h_gpu_mem.swap(gm);
         // each node's active pods in UID order: the shared-GPU guards of addTaskResources are order sensitive (nodes_fake/nodes.go:289-302 adds tasks by UID)
         std::vector<int32_t> np_off((size_t)N + 1, 0), np_pods;
         if (shared) {
@@ -755,7 +777,11 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
             for (int n = 0; n < N; n++) np_off[n + 1] += np_off[n];
             np_pods.resize(order.size()); std::vector<int32_t> fillp(np_off.begin(), np_off.end() - 1);
             for (int p : order) np_pods[fillp[prep.pod_node[p]]++] = p;
-        }
+            // (kai_session_update edits these lists by the delta: every pod's UID rank, each node's list with the ranks)
+            core->np_uid.assign(s->pod_uid_rank, s->pod_uid_rank + P); core->np_lists.assign((size_t)N, {});
+            for (int n = 0; n < N; n++) for (int k = np_off[n]; k < np_off[n + 1]; k++) core->np_lists[(size_t)n].push_back({s->pod_uid_rank[np_pods[k]], np_pods[k]});
+        } else { core->np_uid.clear(); core->np_lists.clear(); }
+        core->np_cap = np_pods.size();
         { const int32_t* t; TRY(dupload(core, &t, np_off.data(), np_off.size())); core->d_np_off = const_cast<int32_t*>(t);
           TRY(dupload(core, &t, np_pods.data(), np_pods.size())); core->d_np_pods = const_cast<int32_t*>(t); }
     }
@@ -821,6 +847,7 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
             [&](void* d, const void* h, size_t n) -> int { return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, core->stream) == hipSuccess ? 0 : (int)KAI_ERR_HIP; },
             core->world, core->rank, core->shard_k);
         if (rcb) return fail(core, rcb, "batch path buffers");
+        core->bt_pools = c.bt; core->bt_alloc = c.bt.enabled != 0; core->bt_C = c.C;
         if (shared) c.bt.enabled = 0; }
     // keep the initial dynamic state in HBM so that kai_session_reset needs no host traffic
     TRY(dalloc(core, &core->d_status0, (size_t)P)); TRY(dalloc(core, &core->d_node0, (size_t)P)); TRY(dalloc(core, &core->d_shares0, (size_t)std::max(Q, 1) * 3));
@@ -885,10 +912,8 @@ int kai_session_open(kai_core* core, const kai_snapshot_soa* s) {
     return rc;
 }
 
-int kai_session_reset(kai_core* core) {
-    if (!core) return KAI_ERR_INVALID_ARG;
-    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
-    HIP_TRY(core, hipSetDevice(core->device));
+// the session's dynamic state from the HBM-resident snapshot: kai_session_reset, and kai_session_update after its scatter
+static int reset_state(kai_core* core) {
     KaiCtx& c = core->ctx;
     const size_t RN = (size_t)c.R * c.N;
     HIP_TRY(core, hipEventRecord(core->ev0, core->stream));
@@ -912,6 +937,277 @@ int kai_session_reset(kai_core* core) {
     float ms = 0; HIP_TRY(core, hipEventElapsedTime(&ms, core->ev0, core->ev1));
     core->stats.upload_ms = ms;
     return KAI_OK;
+}
+
+int kai_session_reset(kai_core* core) {
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    HIP_TRY(core, hipSetDevice(core->device));
+    return reset_state(core);
+}
+
+// ---- kai_session_update: a pod / node delta applied to the open session's snapshot (include/kai_core.h).  Phases: (1) the arguments, on the host; (2) the delta staged
+// and sent in one copy, k_delta_gather reads the snapshot's side of every changed pod (no write); (3) the open's refusals against S', on the host; (4) the counters the
+// open derives by walking the pods and nodes, adjusted old -> new, and the class table ranked again (host, proportional to the delta); (5) k_apply_delta scatters into
+// the baselines, the class labels are re-derived if the table changed, and the session math is re-derived on the device as kai_session_reset does.
+static constexpr int32_t KD_ACTIVE = KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING;
+
+static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote) {
+    const bool prof = std::getenv("KAI_PROF") != nullptr;  // host clocks of the update (stderr), as kai_session_open reports its own
+    const auto t0 = std::chrono::steady_clock::now();
+    auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    int gpu_nodes_after = -1;
+    KaiCtx& c = core->ctx; HostPrep& prep = core->prep; SharedPods& sp = core->sp;
+    const int N = c.N, P = c.P, R = c.R, NP = dl->n_pods, NN = dl->n_nodes;
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- (2) staging: [pod | status | node | group | node | flags] int32, then [R][NN] doubles; the gather's output and counters behind it
+    auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int NNcap = NN + (core->legacy_on ? 2 * NP : 0);  // node entries: the delta's, and the nodes whose legacy-MIG bit a pod of the delta changes
+    const size_t o_i32 = 0, n_i32 = (size_t)4 * NP + 2 * NNcap, o_f64 = up8(n_i32 * 4), o_out = up8(o_f64 + (size_t)R * NNcap * 8), o_cnt = up8(o_out + (size_t)4 * NP * 4), total = o_cnt + 256;
+    if (total > core->dl_pin_bytes) {
+        if (core->dl_pin) (void)hipHostFree(core->dl_pin);
+        core->dl_pin = nullptr; core->dl_pin_bytes = 0;
+        void* h = nullptr; HIP_TRY(core, hipHostMalloc(&h, total + total / 4, hipHostMallocDefault)); core->dl_pin = static_cast<unsigned char*>(h); core->dl_pin_bytes = total + total / 4;
+    }
+    if (total > core->dl_dev_bytes) {
+        if (core->dl_dev) (void)hipFree(core->dl_dev);
+        core->dl_dev = nullptr; core->dl_dev_bytes = 0;
+        void* d = nullptr; HIP_TRY(core, hipMalloc(&d, total + total / 4)); core->dl_dev = static_cast<unsigned char*>(d); core->dl_dev_bytes = total + total / 4;
+    }
+    if (!core->d_rank) {  // caller's node index -> engine index (name rank) on the device, once per session
+        uint32_t* t = nullptr; int rc = dalloc(core, &t, (size_t)std::max(N, 1)); if (rc) return rc;
+        if (N) HIP_TRY(core, hipMemcpyAsync(t, prep.rank_of.data(), (size_t)N * 4, hipMemcpyHostToDevice, core->stream));
+        core->d_rank = t;
+    }
+    int32_t* h32 = reinterpret_cast<int32_t*>(core->dl_pin + o_i32); double* h64 = reinterpret_cast<double*>(core->dl_pin + o_f64);
+    int32_t *hp = h32, *hs = h32 + NP, *hn = h32 + 2 * NP, *hg = h32 + 3 * NP, *hnode = h32 + 4 * NP; uint32_t* hflags = reinterpret_cast<uint32_t*>(h32 + 4 * NP + NN);
+    std::vector<int32_t> eng((size_t)NN);  // the delta's nodes in engine order (the node rows the host keeps are)
+    for (int k = 0; k < NN; k++) eng[(size_t)k] = (int32_t)prep.rank_of[(size_t)dl->node[k]];
+    for (int i = 0; i < NP; i++) {
+        const int p = dl->pod[i]; hp[i] = p; hs[i] = dl->pod_status[i]; hn[i] = dl->pod_node[i];
+        hg[i] = dl->pod_gpu_group ? (sp.shared.size() > (size_t)p && sp.shared[(size_t)p] ? dl->pod_gpu_group[i] : -1) : KD_KEEP;  // the open's rule: a group only on a shared-GPU request
+    }
+    auto node_row = [&](int k, int r) { const int e = eng[(size_t)k]; return dl->node_allocatable ? dl->node_allocatable[(size_t)r * NN + k] : prep.node_alloc[(size_t)r * N + e]; };
+    for (int k = 0; k < NN; k++) {
+        const int e = eng[(size_t)k]; hnode[k] = dl->node[k];
+        hflags[k] = dl->node_flags ? ((dl->node_flags[k] & 0x0FFFFFFFu) | (prep.node_flags[(size_t)e] & 0xF0000000u)) : prep.node_flags[(size_t)e];  // the caller's bits masked as the open does, the library's own kept
+        for (int r = 0; r < R; r++) h64[(size_t)r * NN + k] = node_row(k, r);
+    }
+    unsigned char* dv = core->dl_dev;
+    DeltaView v{reinterpret_cast<const int32_t*>(dv), reinterpret_cast<const int32_t*>(dv) + NP, reinterpret_cast<const int32_t*>(dv) + 2 * NP, reinterpret_cast<const int32_t*>(dv) + 3 * NP,
+                reinterpret_cast<const int32_t*>(dv) + 4 * NP, reinterpret_cast<const uint32_t*>(dv) + 4 * NP + NN, reinterpret_cast<const double*>(dv + o_f64), NP, NN, R, N, core->d_rank};
+    int32_t* d_out = reinterpret_cast<int32_t*>(dv + o_out); int32_t* d_cnt = reinterpret_cast<int32_t*>(dv + o_cnt);
+    HIP_TRY(core, hipMemsetAsync(d_cnt, 0, 256, core->stream));
+    HIP_TRY(core, hipMemcpyAsync(dv, core->dl_pin, o_out, hipMemcpyHostToDevice, core->stream));
+    if (NP) hipLaunchKernelGGL(k_delta_gather, dim3((NP + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, v, (const int32_t*)core->d_status0, (const int32_t*)core->d_node0,
+                               (const int32_t*)core->d_group0, (const uint32_t*)KAI_VP(c.p_flags), d_out, d_cnt);
+    HIP_TRY(core, hipGetLastError());
+    HIP_TRY(core, hipMemcpyAsync(core->dl_pin + o_out, d_out, o_cnt + 256 - o_out, hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    const int32_t* old_st = reinterpret_cast<const int32_t*>(core->dl_pin + o_out); const int32_t* old_nd = old_st + NP; const int32_t* old_gr = old_st + 2 * NP;
+    const uint32_t* pflag = reinterpret_cast<const uint32_t*>(old_st + 3 * NP); const int32_t* cnt = reinterpret_cast<const int32_t*>(core->dl_pin + o_cnt);
+    // ---- (3) the open's refusals on S' (the pods outside the delta passed them when S was opened)
+    for (int i = 0; i < NP; i++) if ((pflag[i] & KAI_POD_CPU_FALLBACK) && hs[i] == KAI_POD_PENDING) return fail(core, KAI_ERR_UNSUPPORTED, "a pending pod is flagged KAI_POD_CPU_FALLBACK: leave its job to the host path");
+    for (int i = 0; i < NP; i++) if ((pflag[i] & KAI_POD_GPU_UNMODELLED) && (hs[i] & KD_ACTIVE)) return fail(core, KAI_ERR_UNSUPPORTED, "an active pod holds GPU state the device does not model (gpu-memory / several fractional devices / MIG / DRA): its node's idle GPUs would be overstated");
+    auto has_gpus = [&](auto row) { if (row(KAI_RES_GPU) > 0) return true; for (int r = KAI_RES_PODS + 1; r < R && r < KAI_MAX_RES; r++) if (sp.mig_g[r] > 0 && row(r) > 0) return true; return false; };
+    if (core->gm_guard && dl->node_allocatable) {  // the open's rule on S': one GPU memory size among the nodes that have GPUs (SharedPods::build)
+        int joined = 0, left = 0; int64_t v = -1; bool mixed = false;
+        for (int k = 0; k < NN; k++) {
+            const int e = eng[(size_t)k];
+            const bool was = has_gpus([&](int r) { return prep.node_alloc[(size_t)r * N + e]; }), is = has_gpus([&](int r) { return node_row(k, r); });
+            if (was && !is) left++;
+            if (!was && is) { joined++; const int64_t m = core->h_gpu_mem[(size_t)e]; if (v < 0) v = m; else if (m != v) mixed = true; }
+        }
+        if (joined || left) {
+            const bool stay = sp.n_gpu_nodes - left > 0;  // nodes of S that keep their GPUs: all of them carry sp.M
+            if (mixed || (stay && joined && v != sp.M)) return fail(core, KAI_ERR_UNSUPPORTED, "shared GPUs with different node_gpu_memory values: leave the cycle to the host path");
+            const int64_t m_new = stay ? sp.M : joined ? v : core->h_gpu_mem[(size_t)prep.rank_of[0]];
+            if (m_new != sp.M) return fail(core, KAI_ERR_UNSUPPORTED, "kai_session_update: the cluster's GPU memory size would change (every GPU node replaced): open the new snapshot");
+            gpu_nodes_after = sp.n_gpu_nodes + joined - left;
+        }
+    }
+    // ---- (4) from here on the session's own state changes: a failure closes the session (kai_session_update)
+    wrote = true;
+    const auto t1 = std::chrono::steady_clock::now();
+    if (gpu_nodes_after >= 0) core->sp.n_gpu_nodes = gpu_nodes_after;
+    prep.n_relpipe += cnt[0];
+    if (prep.keyed) for (int i = 0; i < NP; i++) {
+        const int p = hp[i]; const int64_t d = (hs[i] == KAI_POD_PENDING ? 1 : 0) - (old_st[i] == KAI_POD_PENDING ? 1 : 0);
+        if (!d) continue;
+        if (sp.any && sp.shared[(size_t)p]) prep.n_pend_shared += d; else prep.cfreq[(size_t)prep.pod_key[(size_t)p]] += d;
+    }
+    auto new_node = [&](int i) { return hn[i] >= 0 ? (int)prep.rank_of[(size_t)hn[i]] : -1; };
+    std::vector<int32_t> touched;  // engine nodes whose legacy-MIG bit may change (written with the delta's nodes)
+    if (core->legacy_on) for (int i = 0; i < NP; i++) {
+        if (!(pflag[i] & KAI_POD_LEGACY_MIG)) continue;
+        const int on = (old_st[i] & KD_ACTIVE) ? old_nd[i] : -1, nn = (hs[i] & KD_ACTIVE) ? new_node(i) : -1;
+        if (on == nn) continue;
+        if (on >= 0) { core->legacy_cnt[(size_t)on]--; touched.push_back(on); }
+        if (nn >= 0) { core->legacy_cnt[(size_t)nn]++; touched.push_back(nn); }
+    }
+    // nodes: the class guard's and the exact-sum guard's counts, the host's rows (engine order), the legacy-MIG bit
+    for (int k = 0; k < NN; k++) {
+        const int e = eng[(size_t)k];
+        if (dl->node_allocatable) {
+            if (!prep.nsum_ready) prep.build_node_sums(R, N);  // (once per session: the exact-sum guard's node counts, from the rows before this delta)
+            for (int t = 0; t < 2; t++) {
+                const int r = t == 0 ? KAI_RES_CPU : KAI_RES_GPU;
+                prep.nodes_bad[t] += (HostPrep::node_guard_fails(core->cfg, t, h64[(size_t)r * NN + k], prep.node_gpu_count[(size_t)e]) ? 1 : 0)
+                                   - (HostPrep::node_guard_fails(core->cfg, t, prep.node_alloc[(size_t)r * N + e], prep.node_gpu_count[(size_t)e]) ? 1 : 0);
+            }
+            for (int r = 0; r < R; r++) { prep.nsum[r].add(prep.node_alloc[(size_t)r * N + e], -1); prep.nsum[r].add(h64[(size_t)r * NN + k], +1); prep.node_alloc[(size_t)r * N + e] = h64[(size_t)r * NN + k]; }
+        }
+        prep.node_flags[(size_t)e] = hflags[k];
+    }
+    std::sort(touched.begin(), touched.end()); touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+    std::vector<int32_t> extra;  // legacy-MIG nodes outside the delta: appended as node entries of their own
+    for (int e : touched) {
+        const uint32_t f = core->legacy_cnt[(size_t)e] > 0 ? (prep.node_flags[(size_t)e] | KAI_NODE_LEGACY_MIG_I) : (prep.node_flags[(size_t)e] & ~KAI_NODE_LEGACY_MIG_I);
+        prep.node_flags[(size_t)e] = f;
+        bool listed = false; for (int k = 0; k < NN && !listed; k++) if (eng[(size_t)k] == e) { hflags[k] = f; listed = true; }
+        if (!listed) extra.push_back(e);
+    }
+    // shared GPUs: each node's active pods in UID order, and the groups the cycle may open (next_group0)
+    if (core->shared) {
+        for (int i = 0; i < NP; i++) {
+            const int p = hp[i], on = (old_st[i] & KD_ACTIVE) ? old_nd[i] : -1, nn = (hs[i] & KD_ACTIVE) ? new_node(i) : -1;
+            if (on == nn) continue;
+            const std::pair<uint32_t, int32_t> key{core->np_uid[(size_t)p], p};
+            if (on >= 0) { auto& L = core->np_lists[(size_t)on]; auto it = std::lower_bound(L.begin(), L.end(), key); if (it != L.end() && *it == key) L.erase(it); }
+            if (nn >= 0) { auto& L = core->np_lists[(size_t)nn]; L.insert(std::lower_bound(L.begin(), L.end(), key), key); }
+        }
+        for (int i = 0; i < NP; i++) {
+            if (hg[i] == KD_KEEP || hg[i] == old_gr[i]) continue;
+            if (old_gr[i] >= KAI_NEW_GROUP) { auto it = core->new_groups.find(old_gr[i]); if (it != core->new_groups.end() && --it->second == 0) core->new_groups.erase(it); }
+            if (hg[i] >= KAI_NEW_GROUP) core->new_groups[hg[i]]++;
+        }
+        core->next_group0 = core->new_groups.empty() ? KAI_NEW_GROUP : core->new_groups.rbegin()->first + 1;
+    }
+    // the scalars the open derives: the staged job path, the class table, the exact-sum guard, the batch path
+    prep.fast_ok = (core->cfg.engine_mode == 2 || prep.n_relpipe > 0) ? 0 : 1;
+    const std::vector<ClassRec> old_classes = prep.classes; const std::vector<int> old_remap = prep.remap;
+    if (prep.keyed) prep.rank_classes(core->cfg, sp.any);
+    const bool remap_changed = prep.remap != old_remap;
+    const bool cls_changed = prep.classes.size() != old_classes.size() || (!prep.classes.empty() && std::memcmp(prep.classes.data(), old_classes.data(), prep.classes.size() * sizeof(ClassRec)) != 0);
+    if (dl->node_allocatable && NN) prep.exact_sums = prep.eval_exact_sums(R);  // (only node rows move the guard: the pods' requests are the snapshot's)
+    prep.batch_ok = core->cfg.engine_mode == 0 && R <= 4 && prep.n_heights <= 16 && prep.exact_sums;
+    // ---- (5) the device: the scatter (the legacy-MIG nodes outside the delta as a second, small copy), the class labels, the session math
+    const auto t2 = std::chrono::steady_clock::now();
+    const int NX = NN + (int)extra.size();
+    int32_t* dnode = reinterpret_cast<int32_t*>(dv) + 4 * NP; uint32_t* dflags = reinterpret_cast<uint32_t*>(dv) + 4 * NP + NN;
+    if (!touched.empty()) {  // legacy-MIG bits changed: the node section again, with the nodes outside the delta behind the delta's ([node NX][flags NX], [R][NX]; NX <= NNcap)
+        dflags = reinterpret_cast<uint32_t*>(dv) + 4 * NP + NX;
+        std::vector<int32_t> nid((size_t)NX); std::vector<uint32_t> nfl((size_t)NX); std::vector<double> nal((size_t)R * NX);
+        for (int k = 0; k < NX; k++) {
+            const int e = k < NN ? eng[(size_t)k] : extra[(size_t)(k - NN)];
+            nid[(size_t)k] = prep.perm[(size_t)e]; nfl[(size_t)k] = prep.node_flags[(size_t)e];
+            for (int r = 0; r < R; r++) nal[(size_t)r * NX + k] = prep.node_alloc[(size_t)r * N + e];
+        }
+        std::memcpy(h32 + 4 * NP, nid.data(), (size_t)NX * 4); std::memcpy(h32 + 4 * NP + NX, nfl.data(), (size_t)NX * 4); std::memcpy(h64, nal.data(), (size_t)R * NX * 8);
+        if (NX) { HIP_TRY(core, hipMemcpyAsync(dnode, h32 + 4 * NP, (size_t)2 * NX * 4, hipMemcpyHostToDevice, core->stream));
+                  HIP_TRY(core, hipMemcpyAsync(dv + o_f64, h64, (size_t)R * NX * 8, hipMemcpyHostToDevice, core->stream)); }
+    }
+    v.node = dnode; v.node_flags = dflags; v.n_nodes = NX;
+    if (NP + NX) hipLaunchKernelGGL(k_apply_delta, dim3((NP + NX + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, v, core->d_status0, core->d_node0, core->d_group0,
+                                    (double*)KAI_VP(c.n_alloc), (uint32_t*)KAI_VP(c.n_flags));
+    HIP_TRY(core, hipGetLastError());
+    int rc;
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    if (cls_changed || remap_changed) {
+        const int C = (int)prep.classes.size();
+        if (C > core->cls_cap) {  // more classes than the session's arrays hold: new ones for KAI_CMAX (the victim actions' replicas are laid out again)
+            TRY(dalloc_f(core, c.cls, (size_t)KAI_CMAX));
+            TRY(dzero_f(core, c.sum1_key, (size_t)KAI_CMAX * std::max(c.NB, 1))); TRY(dzero_f(core, c.sum1_node, (size_t)KAI_CMAX * std::max(c.NB, 1)));
+            core->cls_cap = KAI_CMAX; core->mw_world = 0;
+        }
+        if (C) HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.cls), prep.classes.data(), (size_t)C * sizeof(ClassRec), hipMemcpyHostToDevice, core->stream));
+        c.C = C;
+    }
+    if (remap_changed && P) {
+        if (!core->d_pkey) {  // the pods' request keys, once per session
+            int32_t* t = nullptr; TRY(dalloc(core, &t, (size_t)P));
+            HIP_TRY(core, hipMemcpyAsync(t, prep.pod_key.data(), (size_t)P * 4, hipMemcpyHostToDevice, core->stream)); core->d_pkey = t;
+        }
+        if (prep.remap.size() > core->remap_cap) { int32_t* t = nullptr; TRY(dalloc(core, &t, prep.remap.size())); core->d_remap = t; core->remap_cap = prep.remap.size(); }
+        std::vector<int32_t> rm(prep.remap.begin(), prep.remap.end());
+        if (!rm.empty()) HIP_TRY(core, hipMemcpyAsync(core->d_remap, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, core->stream));
+        hipLaunchKernelGGL(k_class_remap, dim3((P + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, P, (const int32_t*)core->d_pkey, (const uint8_t*)KAI_VP(c.p_shared), sp.any ? 1 : 0,
+                           (const int32_t*)core->d_remap, (int32_t*)KAI_VP(c.p_scls));
+        HIP_TRY(core, hipGetLastError());
+        HIP_TRY(core, hipStreamSynchronize(core->stream));  // (rm dies with this scope)
+    }
+    if (core->shared) {  // each node's active pods, flattened (a session with shared-GPU requests: O(nodes + active pods))
+        std::vector<int32_t> np_off((size_t)N + 1, 0), np_pods;
+        for (int n = 0; n < N; n++) np_off[(size_t)n + 1] = np_off[(size_t)n] + (int32_t)core->np_lists[(size_t)n].size();
+        np_pods.reserve((size_t)np_off[(size_t)N]);
+        for (int n = 0; n < N; n++) for (const auto& x : core->np_lists[(size_t)n]) np_pods.push_back(x.second);
+        if (np_pods.size() > core->np_cap) { int32_t* t = nullptr; TRY(dalloc(core, &t, np_pods.size())); core->d_np_pods = t; core->np_cap = np_pods.size(); }
+        HIP_TRY(core, hipMemcpyAsync(core->d_np_off, np_off.data(), np_off.size() * 4, hipMemcpyHostToDevice, core->stream));
+        if (!np_pods.empty()) HIP_TRY(core, hipMemcpyAsync(core->d_np_pods, np_pods.data(), np_pods.size() * 4, hipMemcpyHostToDevice, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+    }
+    // the context's scalars as the open sets them from the snapshot
+    c.use_index = (c.C > 0 && !core->idx_forced_off) ? 1 : 0;
+    c.all_tracked = (core->shared || sp.mig) ? 0 : prep.all_tracked;
+    core->fast_ok0 = core->fast_forced_off ? 0 : prep.fast_ok; c.fast_ok = core->fast_ok0;
+    c.exact_sums = prep.exact_sums;
+    {   const bool want = prep.batch_ok && c.use_index && c.all_tracked && c.fast_ok && c.R <= 4 && (c.plugins & KAI_PLUGIN_PROPORTION) && !core->shared;
+        if (!want) c.bt.enabled = 0;
+        else if (core->bt_alloc && core->bt_C >= c.C) { c.bt = core->bt_pools; c.bt.enabled = 1; }
+        else {
+            const int rcb = batch_bind(c, prep,
+                [&](size_t bytes) -> void* { char* q = nullptr; if (dalloc(core, &q, bytes)) return nullptr; if (hipMemsetAsync(q, 0, bytes, core->stream) != hipSuccess) return nullptr; return q; },
+                [&](void* d, const void* h, size_t n) -> int { return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, core->stream) == hipSuccess ? 0 : (int)KAI_ERR_HIP; },
+                core->world, core->rank, core->shard_k);
+            if (rcb) return fail(core, rcb, "batch path buffers");
+            HIP_TRY(core, hipStreamSynchronize(core->stream));  // (the tables batch_bind uploads are the handle's host prep: stable, but keep the order plain)
+            core->bt_pools = c.bt; core->bt_alloc = c.bt.enabled != 0; core->bt_C = c.C;
+        }
+    }
+#undef TRY
+    { const int rc2 = reset_state(core); if (rc2) return rc2; }
+    HIP_TRY(core, hipMemcpyAsync(core->d_ctx, &core->ctx, sizeof(KaiCtx), hipMemcpyHostToDevice, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    core->err = "ok";
+    if (prof) { const auto t3 = std::chrono::steady_clock::now();
+                std::fprintf(stderr, "kai update: %d pods %d nodes | stage + gather + checks %.3f, host bookkeeping %.3f, device (scatter, classes, re-derivation) %.3f | total %.3f ms\n",
+                             NP, NN, tms(t0, t1), tms(t1, t2), tms(t2, t3), tms(t0, t3)); }
+    return KAI_OK;
+}
+
+int kai_session_update(kai_core* core, const kai_session_delta* d) {
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (!d) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: NULL delta");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_session_update: a handle of a sharded group (open the new snapshot on every rank)");
+    if (d->version != KAI_DELTA_VERSION) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: wrong delta version");
+    const int N = core->ctx.N, P = core->ctx.P, NP = d->n_pods, NN = d->n_nodes;
+    if (NP < 0 || NN < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: negative count");
+    if (NP > 0 && (!d->pod || !d->pod_status || !d->pod_node)) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a required pod array is NULL");
+    if (NN > 0 && !d->node) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: the node array is NULL");
+    try {
+        for (int i = 0; i < NP; i++) {
+            if (d->pod[i] < 0 || d->pod[i] >= P) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: pod index out of range");
+            if (d->pod_node[i] < -1 || d->pod_node[i] >= N) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: pod_node out of range");
+        }
+        for (int k = 0; k < NN; k++) if (d->node[k] < 0 || d->node[k] >= N) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: node index out of range");
+        {   std::vector<int32_t> a(d->pod, d->pod + NP); std::sort(a.begin(), a.end());
+            if (std::adjacent_find(a.begin(), a.end()) != a.end()) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a pod is listed twice");
+            std::vector<int32_t> b(d->node, d->node + NN); std::sort(b.begin(), b.end());
+            if (std::adjacent_find(b.begin(), b.end()) != b.end()) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a node is listed twice"); }
+    } catch (const std::bad_alloc&) { core->err = "kai_session_update: out of host memory"; return KAI_ERR_NO_MEMORY; }
+    bool wrote = false; int rc;
+    try { rc = update_impl(core, d, wrote); }
+    catch (const std::bad_alloc&) { core->err = "kai_session_update: out of host memory"; rc = KAI_ERR_NO_MEMORY; }
+    catch (const std::exception& e) { core->err = std::string("kai_session_update: ") + e.what(); rc = KAI_ERR_INVALID_ARG; }
+    catch (...) { core->err = "kai_session_update: unknown exception"; rc = KAI_ERR_INVALID_ARG; }
+    if (rc != KAI_OK && wrote) {  // the writes began: the session is no longer the snapshot it was, nor S' — closed, as a failed open leaves it
+        const std::string why = core->err;
+        if (core->stream) (void)hipStreamSynchronize(core->stream);
+        free_session(core);
+        core->err = why;
+    } else if (rc != KAI_OK && core->stream) (void)hipStreamSynchronize(core->stream);
+    return rc;
 }
 
 int kai_queue_shares(kai_core* core, kai_queue_share* out, int cap) {

@@ -1,0 +1,83 @@
+// kai_delta.hpp — kernels of kai_session_update (include/kai_core.h): a pod / node delta applied to the HBM-resident snapshot of an open session.
+//
+// The host stages the delta in ONE pinned buffer and sends it with one copy (DeltaView: the arrays inside that buffer).  k_delta_gather reads what the
+// snapshot holds for every changed pod (status, node, shared-GPU group, flags) without writing the session, so that every refusal is decided before the
+// first write; it also adds up the delta's effect on the count of Releasing / Pipelined pods (wavefront reductions, one atomic per workgroup; the host
+// adjusts the pending pods per request key itself, from the old statuses gathered here).  k_apply_delta then
+// scatters the delta into the baselines kai_session_reset restores (d_status0 / d_node0 / d_group0) and into the nodes' allocatable rows and flags,
+// mapping the caller's node indices through the name-rank permutation.  k_class_remap re-labels every pod's scan class when the class table changed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kai_engine.hpp"
+
+namespace kai {
+
+constexpr int KD_TB = 256;        // threads per workgroup of the delta kernels (4 wavefronts)
+constexpr int KD_KEEP = INT32_MIN;  // a group entry the delta leaves unchanged
+constexpr int KD_NCNT = 1;        // per-session counters adjusted by a delta: [0] Releasing or Pipelined pods
+
+// The delta as it sits in the staging buffer (device addresses of the one upload).  Pod entries: index, new status, new node (caller's index or -1),
+// new group (KD_KEEP = unchanged; the host has already applied the open's rule "a group only on a shared-GPU request").  Node entries: index (caller's),
+// new flags (already masked to the public bits, the library's own bits merged back by the host), new allocatable [R][n_nodes].
+struct DeltaView {
+    const int32_t* pod; const int32_t* pod_status; const int32_t* pod_node; const int32_t* pod_group;
+    const int32_t* node; const uint32_t* node_flags; const double* node_alloc;
+    int32_t n_pods, n_nodes, R, N;
+    const uint32_t* rank;  // [N] node_name_rank: caller's node index -> engine index
+};
+
+__device__ __forceinline__ int kd_wave_sum(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Read-only: what the session's snapshot holds for each changed pod, and the counter adjustments old -> new.
+__global__ void __launch_bounds__(KD_TB) k_delta_gather(DeltaView d, const int32_t* __restrict__ status0, const int32_t* __restrict__ node0, const int32_t* __restrict__ group0,
+                                                        const uint32_t* __restrict__ flags, int32_t* __restrict__ out, int32_t* __restrict__ counters) {
+    __shared__ int part[KD_TB / 64][KD_NCNT];
+    const int i = blockIdx.x * KD_TB + threadIdx.x;
+    int drel = 0;
+    if (i < d.n_pods) {
+        const int p = d.pod[i];
+        const int so = status0[p], sn = d.pod_status[i];
+        out[i] = so; out[d.n_pods + i] = node0[p]; out[2 * d.n_pods + i] = group0[p]; out[3 * d.n_pods + i] = (int32_t)flags[p];
+        const int rp = KAI_POD_RELEASING | KAI_POD_PIPELINED;
+        drel = ((sn & rp) ? 1 : 0) - ((so & rp) ? 1 : 0);
+    }
+    drel = kd_wave_sum(drel);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) part[w][0] = drel;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0;
+        for (int k = 0; k < KD_TB / 64; k++) a += part[k][0];
+        if (a) atomicAdd(&counters[0], a);
+    }
+}
+
+// The scatter: one thread per changed pod, then one per changed node (every index was range-checked by the host).
+__global__ void __launch_bounds__(KD_TB) k_apply_delta(DeltaView d, int32_t* __restrict__ status0, int32_t* __restrict__ node0, int32_t* __restrict__ group0,
+                                                       double* __restrict__ n_alloc, uint32_t* __restrict__ n_flags) {
+    const int i = blockIdx.x * KD_TB + threadIdx.x;
+    if (i < d.n_pods) {
+        const int p = d.pod[i], n = d.pod_node[i];
+        status0[p] = d.pod_status[i];
+        node0[p] = n >= 0 ? (int32_t)d.rank[n] : -1;
+        if (d.pod_group[i] != KD_KEEP) group0[p] = d.pod_group[i];
+    } else if (i < d.n_pods + d.n_nodes) {
+        const int k = i - d.n_pods, e = (int)d.rank[d.node[k]];
+        n_flags[e] = d.node_flags[k];
+        for (int r = 0; r < d.R; r++) n_alloc[(size_t)r * d.N + e] = d.node_alloc[(size_t)r * d.n_nodes + k];
+    }
+}
+
+// Every pod's scan class from its request key (a new class table: kai_host_prep.hpp rank_classes); a shared-GPU request is in no class.
+__global__ void __launch_bounds__(KD_TB) k_class_remap(int P, const int32_t* __restrict__ pod_key, const uint8_t* __restrict__ shared, int shared_on, const int32_t* __restrict__ remap,
+                                                       int32_t* __restrict__ scls) {
+    const int p = blockIdx.x * KD_TB + threadIdx.x;
+    if (p < P) scls[p] = (shared_on && shared[p]) ? -1 : remap[pod_key[p]];
+}
+
+}  // namespace kai

@@ -25,6 +25,7 @@ struct SharedPods {
     bool any = false, mig = false, on = false; std::string err;  // any: shared-GPU requests; mig: some resource row is a MIG profile; on = any || mig: the arrays below are in use
     raw_vector<uint8_t> shared, kind; raw_vector<int64_t> mem, gmem; raw_vector<double> acc_gpu, pend_gpu, quota_gpu, mig_q;  // every element is written by build()'s parallel loop
     int32_t mig_g[KAI_MAX_RES] = {0}; int64_t mig_m[KAI_MAX_RES] = {0};
+    int64_t M = 100; int n_gpu_nodes = 0;  // the cluster's one GPU memory size and the nodes that have GPUs (counted with node_gpu_memory; kai_session_update re-checks the rule on a node delta)
     enum { K_MIG = 1, K_LEGACY = 2, K_REGULAR = 4, K_GPUS = 8 };  // PodInfo: IsMigCandidate / IsLegacyMIGtask / IsRegularGPURequest / ResReq.GPUs() > 0
     static bool has(const kai_snapshot_soa* s) {
         if (!s->pod_gpu_portion && !s->pod_gpu_memory) return false;
@@ -48,9 +49,9 @@ struct SharedPods {
         // one GPU memory size for the cluster — among the nodes that HAVE devices: a node without the gpu.memory label carries DefaultGpuMemory = 100 (node_info.go:673-687),
         // which on a CPU-only node is never read
         auto has_gpus = [&](int i) { if (s->node_allocatable[(size_t)KAI_RES_GPU * N + i] > 0) return true; for (int r = KAI_RES_PODS + 1; r < s->n_res && r < KAI_MAX_RES; r++) if (mig_g[r] > 0 && s->node_allocatable[(size_t)r * N + i] > 0) return true; return false; };
-        int first_gpu = -1;
-        if (s->node_gpu_memory) for (int i = 0; i < N; i++) if (has_gpus(i)) { if (first_gpu < 0) first_gpu = i; else if (any && s->node_gpu_memory[i] != s->node_gpu_memory[first_gpu]) { err = "shared GPUs with different node_gpu_memory values: leave the cycle to the host path"; return false; } }
-        const int64_t M = (s->node_gpu_memory && N > 0) ? s->node_gpu_memory[first_gpu >= 0 ? first_gpu : 0] : 100;
+        int first_gpu = -1; n_gpu_nodes = 0;
+        if (s->node_gpu_memory) for (int i = 0; i < N; i++) if (has_gpus(i)) { n_gpu_nodes++; if (first_gpu < 0) first_gpu = i; else if (any && s->node_gpu_memory[i] != s->node_gpu_memory[first_gpu]) { err = "shared GPUs with different node_gpu_memory values: leave the cycle to the host path"; return false; } }
+        M = (s->node_gpu_memory && N > 0) ? s->node_gpu_memory[first_gpu >= 0 ? first_gpu : 0] : 100;
         // per pod, independent of the others: chunks of the pod range on the host's cores; the error reported is the one of the lowest pod
         const int K = chunk_count((size_t)P);
         std::vector<std::string> cerr((size_t)K);
@@ -95,7 +96,7 @@ struct HostPrep {
     std::vector<QShare> shares;
     int n_levels = 0;
     // nodes in name-rank order: perm[i] = caller's index of the node with rank i
-    std::vector<int32_t> perm, node_gpu_count, node_class;
+    std::vector<int32_t> perm, node_gpu_count, node_class; std::vector<uint32_t> rank_of;  // rank_of = the inverse of perm (kai_session_update maps a delta's node indices)
     raw_vector<int32_t> pod_node, pod_nominated;
     std::vector<double> node_alloc; std::vector<uint32_t> node_flags;
     // scan classes
@@ -165,8 +166,8 @@ struct HostPrep {
         for (int g = 0; g < s->n_groups; g++) if (s->group_parent && s->group_parent[g] < -1) return fail("group_parent out of range");
         lap(0);
         // ---- nodes: permute into name-rank order (framework/session.go:480-485 breaks score ties by node name)
-        perm.assign(N, -1);
-        for (int i = 0; i < N; i++) { uint32_t rk = s->node_name_rank[i]; if (rk >= (uint32_t)N || perm[rk] >= 0) return fail("node_name_rank must be a permutation of 0..N-1"); perm[rk] = i; }
+        perm.assign(N, -1); rank_of.resize(N);
+        for (int i = 0; i < N; i++) { uint32_t rk = s->node_name_rank[i]; if (rk >= (uint32_t)N || perm[rk] >= 0) return fail("node_name_rank must be a permutation of 0..N-1"); perm[rk] = i; rank_of[i] = rk; }
         node_alloc.resize((size_t)R * N); node_flags.resize(N); node_gpu_count.resize(N); node_class.resize(N);
         for (int i = 0; i < N; i++) {
             int o = perm[i];
@@ -288,6 +289,45 @@ struct HostPrep {
         return 0;
     }
 
+    // The exact-sum guard's operands, kept for kai_session_update.  The pods' side per resource (their requests never change in a session): psum[0 .. pods_known),
+    // pods_never = some request fails, the guard can never pass.  The nodes' side as counts that a node delta can adjust (values that fail, values per set bit, the sum):
+    // nsum, built from node_alloc by the first update that carries allocatable (build_node_sums) — the open only takes the OR and the sum it always took.
+    static bool sum_value_ok(double x) { return x >= 0 && x < 9.2e18 && x == (double)(uint64_t)x; }
+    struct NodeSum {
+        int64_t bad = 0; int64_t bit[64] = {0}; unsigned __int128 sum = 0;
+        void add(double x, int sign) {
+            if (!sum_value_ok(x)) { bad += sign; return; }
+            const uint64_t u = (uint64_t)x;
+            for (uint64_t b = u; b; b &= b - 1) bit[__builtin_ctzll(b)] += sign;
+            if (sign > 0) sum += u; else sum -= u;
+        }
+        void merge(const NodeSum& o) { bad += o.bad; for (int b = 0; b < 64; b++) bit[b] += o.bit[b]; sum += o.sum; }
+        uint64_t bits() const { uint64_t o = 0; for (int b = 0; b < 64; b++) if (bit[b] > 0) o |= (uint64_t)1 << b; return o; }
+    };
+    struct PodSum { bool ok = true; uint64_t bits = 0; unsigned __int128 sum = 0; };
+    NodeSum nsum[KAI_MAX_RES]; PodSum psum[KAI_MAX_RES]; int pods_known = 0; bool pods_never = false, nsum_ready = false;
+    void build_node_sums(int R, int N) {  // node_alloc is [R][N] in engine order; chunks of the nodes on the host's cores, merged
+        for (int r = 0; r < R; r++) {
+            const double* v = node_alloc.data() + (size_t)r * N;
+            std::vector<NodeSum> acc((size_t)chunk_count((size_t)N));
+            parallel_chunks((size_t)N, [&](int ci, size_t i0, size_t i1) { NodeSum a; for (size_t i = i0; i < i1; i++) a.add(v[i], +1); acc[(size_t)ci] = a; });
+            nsum[r] = NodeSum{}; for (const NodeSum& a : acc) nsum[r].merge(a);
+        }
+        nsum_ready = true;
+    }
+    int eval_exact_sums(int R) const {  // (with nsum_ready and pods_known == R unless pods_never)
+        if (pods_never) return 0;
+        for (int r = 0; r < R; r++) {
+            if (nsum[r].bad > 0 || !psum[r].ok) return 0;
+            const uint64_t bits = nsum[r].bits() | psum[r].bits;
+            if (!bits) continue;
+            const int tz = __builtin_ctzll(bits);
+            const unsigned __int128 lim = (unsigned __int128)1 << 52;
+            if ((nsum[r].sum >> tz) >= lim || (psum[r].sum >> tz) >= lim) return 0;
+        }
+        return 1;
+    }
+
     void build_batch(const kai_config& cfg, const kai_snapshot_soa* s) {
         const int N = s->n_nodes, P = s->n_pods, Q = s->n_queues, R = s->n_res;
         q_height.assign(Q + 1, 0);
@@ -302,8 +342,8 @@ struct HostPrep {
         for (int i = n_heights > 1 ? h_off[1] : Q + 1; i <= Q; i++) { const int q = h_nodes[i]; if (q < Q) { q_islot[(size_t)q] = i - h_off[1]; n_inner = i - h_off[1] + 1; } }
         for (int q = 0; q < Q; q++) if (child_off[q + 1] == child_off[q]) shape.n_leaves++;
         // exact sums: per resource every quantity is a non-negative integer multiple of one power of two, and the totals stay below 2^53 units
-        exact_sums = 1;
-        for (int r = 0; r < R && exact_sums; r++) {
+        exact_sums = 1; pods_known = 0; pods_never = false; nsum_ready = false;
+        for (int r = 0; r < R; r++) {
             // one pass per array on the host's cores: every value a non-negative integer below 2^63, the OR of all values (its trailing zeros = the common
             // power-of-two unit) and the 128-bit sums of the raw values (sum / unit = the sum of the units: every value is a multiple of the unit)
             struct Acc { bool ok = true; uint64_t bits = 0; unsigned __int128 sum = 0; };
@@ -317,8 +357,12 @@ struct HostPrep {
                 Acc t; for (const Acc& a : acc) { t.ok = t.ok && a.ok; t.bits |= a.bits; t.sum += a.sum; }
                 return t;
             };
-            const Acc an = pass(s->node_allocatable + (size_t)r * N, (size_t)N), ap = pass(s->pod_req + (size_t)r * P, (size_t)P);
-            if (!an.ok || !ap.ok) { exact_sums = 0; break; }
+            const Acc ap = pass(s->pod_req + (size_t)r * P, (size_t)P);
+            psum[r] = PodSum{ap.ok, ap.bits, ap.sum}; pods_known = r + 1;
+            if (!ap.ok) { exact_sums = 0; pods_never = true; break; }  // (a pod request fails: no node delta can make the guard pass)
+            if (!exact_sums) continue;  // (the guard failed on an earlier resource's nodes: the pods' side of this one is still what kai_session_update needs)
+            const Acc an = pass(s->node_allocatable + (size_t)r * N, (size_t)N);
+            if (!an.ok) { exact_sums = 0; continue; }
             const uint64_t bits = an.bits | ap.bits;
             if (!bits) continue;
             const int tz = __builtin_ctzll(bits);
@@ -419,52 +463,59 @@ struct HostPrep {
     // and does not count in the integer guard of the GPU column; the other pods' classes stay indexed, their keys carry the gpusharingorder bit (kai_engine.hpp key_shared_layout).
     // MIG rows keep every scan on brute force (the caller turns the index off).
     const SharedPods* shared_pods = nullptr;  // set by the caller before build() when the snapshot has shared-GPU requests
+    // What the class table is ranked from, kept for kai_session_update (which adjusts it by a delta instead of walking the pods again):
+    //   pod_key: each pod's request key (id in order of first appearance over the pods; -1 with engine_mode 1, where no key is formed); ckeys / cfreq: the keys and their
+    //   PENDING pods that are no shared-GPU request; n_pend_shared: pending shared-GPU requests (they make the index "untracked"); nodes_bad / pods_bad: nodes / pods that
+    //   fail the integer guard of the CPU [0] and GPU [1] placement resource; n_relpipe: pods that are Releasing or Pipelined (the staged job path's verdict); remap: key -> class
+    struct Key { double req[KAI_MAX_RES]; int32_t pc; bool operator<(const Key& o) const { int c = std::memcmp(req, o.req, sizeof req); return c ? c < 0 : pc < o.pc; } };
+    raw_vector<int32_t> pod_key; std::vector<Key> ckeys; std::vector<int64_t> cfreq; std::vector<int> remap;
+    int64_t n_pend_shared = 0, n_relpipe = 0, nodes_bad[2] = {0, 0}; bool pods_bad[2] = {false, false}, keyed = false, nsb_over = false;
+    // a node's quantity of placement resource t (0: CPU, 1: GPU) against the class guard below
+    static bool node_guard_fails(const kai_config& cfg, int t, double a, int32_t gpu_count) {
+        auto integral = [](double v, double lim) { return v >= 0 && v <= lim && v == (double)(int64_t)v; };
+        const int r = t == 0 ? KAI_RES_CPU : KAI_RES_GPU; const int strat = t == 0 ? cfg.cpu_strategy : cfg.gpu_strategy;
+        if (strat == KAI_SPREAD) {
+            double cnt = a;
+            if (r == KAI_RES_GPU && gpu_count >= 0) cnt = (double)gpu_count; else if (r == KAI_RES_GPU) cnt = (double)(int64_t)a;
+            return !integral(a, 4194304.0) || !(cnt >= a) || cnt > 4194304.0;
+        }
+        return !integral(a, 1073741824.0) || (r == KAI_RES_CPU && a == 0);
+    }
     void build_classes(const kai_config& cfg, const kai_snapshot_soa* s) {
         const int N = s->n_nodes, P = s->n_pods, R = s->n_res;
         const uint8_t* sh = (shared_pods && shared_pods->any) ? shared_pods->shared.data() : nullptr;
         par_fill(pod_scls, (size_t)P, -1); classes.clear(); all_tracked = 1;
+        keyed = false; ckeys.clear(); cfreq.clear(); remap.clear(); n_pend_shared = 0;
         // the staged job path needs "fits on Idle+Releasing" == "fits on Idle" for every node: nothing releasing, nothing pipelined
-        fast_ok = cfg.engine_mode == 2 ? 0 : 1;
         auto integral = [](double v, double lim) { return v >= 0 && v <= lim && v == (double)(int64_t)v; };  // (v <= lim < 2^63: the truncation is floor for v >= 0)
-        bool ok_res[2] = {true, true};  // [0] = CPU, [1] = GPU as placement resource
-        const int rr[2] = {KAI_RES_CPU, KAI_RES_GPU};
         for (int t = 0; t < 2; t++) {
-            int r = rr[t]; int strat = t == 0 ? cfg.cpu_strategy : cfg.gpu_strategy;
-            for (int n = 0; n < N && ok_res[t]; n++) {
-                double a = s->node_allocatable[(size_t)r * N + n];
-                if (strat == KAI_SPREAD) {
-                    double cnt = a;
-                    if (r == KAI_RES_GPU && s->node_gpu_count && s->node_gpu_count[n] >= 0) cnt = (double)s->node_gpu_count[n]; else if (r == KAI_RES_GPU) cnt = (double)(int64_t)a;
-                    if (!integral(a, 4194304.0) || !(cnt >= a) || cnt > 4194304.0) ok_res[t] = false;
-                } else {
-                    if (!integral(a, 1073741824.0)) ok_res[t] = false;
-                    if (r == KAI_RES_CPU && a == 0) ok_res[t] = false;
-                }
-            }
+            nodes_bad[t] = 0;
+            for (int n = 0; n < N; n++) if (node_guard_fails(cfg, t, s->node_allocatable[(size_t)(t == 0 ? KAI_RES_CPU : KAI_RES_GPU) * N + n], s->node_gpu_count ? s->node_gpu_count[n] : -1)) nodes_bad[t]++;
         }
-        {   // per pod, one pass on the host's cores: a releasing / pipelined pod anywhere, a CPU or GPU request that is no integer <= 2^30
+        {   // per pod, one pass on the host's cores: releasing / pipelined pods, a CPU or GPU request that is no integer <= 2^30
             const int K = chunk_count((size_t)P);
-            std::vector<unsigned char> flags((size_t)K, 0);
+            std::vector<unsigned char> flags((size_t)K, 0); std::vector<int64_t> relc((size_t)K, 0);
             const double* cpu = s->pod_req + (size_t)KAI_RES_CPU * P; const double* gpu = s->pod_req + (size_t)KAI_RES_GPU * P;
             parallel_chunks((size_t)P, [&](int ci, size_t p0, size_t p1) {
-                unsigned char f = 0;
+                unsigned char f = 0; int64_t nr = 0;
                 for (size_t p = p0; p < p1; p++) {
-                    if (s->pod_status[p] & (KAI_POD_RELEASING | KAI_POD_PIPELINED)) f |= 1;
+                    if (s->pod_status[p] & (KAI_POD_RELEASING | KAI_POD_PIPELINED)) nr++;
                     if (!integral(cpu[p], 1073741824.0)) f |= 2;
                     if (!(sh && sh[p]) && !integral(gpu[p], 1073741824.0)) f |= 4;
                 }
-                flags[(size_t)ci] = f;
+                flags[(size_t)ci] = f; relc[(size_t)ci] = nr;
             });
-            for (unsigned char f : flags) { if (f & 1) fast_ok = 0; if (f & 2) ok_res[0] = false; if (f & 4) ok_res[1] = false; }
+            pods_bad[0] = pods_bad[1] = false; n_relpipe = 0;
+            for (int ci = 0; ci < K; ci++) { if (flags[(size_t)ci] & 2) pods_bad[0] = true; if (flags[(size_t)ci] & 4) pods_bad[1] = true; n_relpipe += relc[(size_t)ci]; }
         }
+        fast_ok = (cfg.engine_mode == 2 || n_relpipe > 0) ? 0 : 1;
         if (cfg.engine_mode == 1) { all_tracked = 0; return; }
-        struct Key { double req[KAI_MAX_RES]; int32_t pc; bool operator<(const Key& o) const { int c = std::memcmp(req, o.req, sizeof req); return c ? c < 0 : pc < o.pc; } };
         // class ids in order of first appearance over the pods.  Chunks of the pod range are classified on the host's cores (a chunk's keys in ITS order of first
         // appearance; a pod usually repeats the key of the pod before it, so that one is compared first), then merged chunk by chunk: the ids come out as in one pass
-        std::map<Key, int> ids; std::vector<Key> keys; std::vector<int64_t> freq; raw_vector<int32_t> pod_cls((size_t)P);  // (every element is written by the classification below)
+        std::map<Key, int> ids; pod_key.resize((size_t)P);  // (every element is written by the classification below)
         {
             const int K = chunk_count((size_t)P);
-            struct Local { std::vector<Key> keys; std::vector<int64_t> freq; bool untracked = false; };
+            struct Local { std::vector<Key> keys; std::vector<int64_t> freq; int64_t untracked = 0; };
             std::vector<Local> loc((size_t)K);
             auto make_key = [&](size_t p, Key& k) { std::memset(&k, 0, sizeof k); for (int r = 0; r < R; r++) { double v = s->pod_req[(size_t)r * P + p]; k.req[r] = v == 0 ? 0.0 : v; } k.pc = s->pod_class ? s->pod_class[p] : 0; };  // folds -0.0
             parallel_chunks((size_t)P, [&](int ci, size_t p0, size_t p1) {
@@ -474,43 +525,52 @@ struct HostPrep {
                     int id;
                     if (last >= 0 && std::memcmp(&L.keys[(size_t)last], &k, sizeof(Key)) == 0) id = last;
                     else { auto it = lid.find(k); if (it == lid.end()) { id = (int)L.keys.size(); lid[k] = id; L.keys.push_back(k); L.freq.push_back(0); } else id = it->second; }
-                    last = id; pod_cls[p] = id;  // chunk-local id for now
-                    if (s->pod_status[p] == KAI_POD_PENDING) { if (sh && sh[p]) L.untracked = true; else L.freq[(size_t)id]++; }
+                    last = id; pod_key[p] = id;  // chunk-local id for now
+                    if (s->pod_status[p] == KAI_POD_PENDING) { if (sh && sh[p]) L.untracked++; else L.freq[(size_t)id]++; }
                 }
             });
             std::vector<std::vector<int>> to_global((size_t)K);
             for (int ci = 0; ci < K; ci++) {
                 Local& L = loc[(size_t)ci]; to_global[(size_t)ci].resize(L.keys.size());
-                if (L.untracked) all_tracked = 0;
+                n_pend_shared += L.untracked;
                 for (size_t i = 0; i < L.keys.size(); i++) {
                     auto it = ids.find(L.keys[i]);
-                    int id; if (it == ids.end()) { id = (int)keys.size(); ids[L.keys[i]] = id; keys.push_back(L.keys[i]); freq.push_back(0); } else id = it->second;
-                    to_global[(size_t)ci][i] = id; freq[(size_t)id] += L.freq[i];
+                    int id; if (it == ids.end()) { id = (int)ckeys.size(); ids[L.keys[i]] = id; ckeys.push_back(L.keys[i]); cfreq.push_back(0); } else id = it->second;
+                    to_global[(size_t)ci][i] = id; cfreq[(size_t)id] += L.freq[i];
                 }
             }
-            parallel_chunks((size_t)P, [&](int ci, size_t p0, size_t p1) { const std::vector<int>& g = to_global[(size_t)ci]; for (size_t p = p0; p < p1; p++) pod_cls[p] = g[(size_t)pod_cls[p]]; });
+            parallel_chunks((size_t)P, [&](int ci, size_t p0, size_t p1) { const std::vector<int>& g = to_global[(size_t)ci]; for (size_t p = p0; p < p1; p++) pod_key[p] = g[(size_t)pod_key[p]]; });
         }
-        std::vector<int> order(keys.size()); for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return freq[a] > freq[b]; });
-        std::vector<int> remap(keys.size(), -1);
+        keyed = true;
+        const int NB = (N + KAI_BLOCK - 1) / KAI_BLOCK, NSB = (NB + 63) / 64;
+        nsb_over = NSB > KAI_NSB_MAX;  // beyond the LDS level: brute force
+        rank_classes(cfg, sh != nullptr);
+        parallel_chunks((size_t)P, [&](int, size_t p0, size_t p1) { for (size_t p = p0; p < p1; p++) pod_scls[p] = (sh && sh[p]) ? -1 : remap[(size_t)pod_key[p]]; });
+    }
+    // The class table from the key frequencies: the KAI_CMAX most frequent admissible keys among PENDING pods, ties in order of first appearance; remap = key -> class or -1.
+    // Sets classes, remap and all_tracked (kai_session_open through build_classes, kai_session_update after adjusting the operands by a delta).
+    void rank_classes(const kai_config& cfg, bool sh) {
+        classes.clear(); all_tracked = n_pend_shared > 0 ? 0 : 1;
+        const bool ok_res[2] = {nodes_bad[0] == 0 && !pods_bad[0], nodes_bad[1] == 0 && !pods_bad[1]};  // [0] = CPU, [1] = GPU as placement resource
+        std::vector<int> order(ckeys.size()); for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cfreq[a] > cfreq[b]; });
+        remap.assign(ckeys.size(), -1);
         for (int id : order) {
-            const Key& k = keys[id];
+            const Key& k = ckeys[id];
             bool cpu_only = !(k.req[KAI_RES_GPU] > 0);
             bool admissible = !(cfg.plugins & KAI_PLUGIN_NODEPLACEMENT) || ok_res[cpu_only ? 0 : 1];
             if (sh && (cfg.plugins & KAI_PLUGIN_NODEPLACEMENT) && (cfg.plugins & KAI_PLUGIN_GPUSHARINGORDER) && (cpu_only ? cfg.cpu_strategy : cfg.gpu_strategy) == KAI_SPREAD) admissible = false;  // no room for the sharing bit above a spread key
-            if (freq[id] == 0) continue;  // only classes that have pending pods are ever queried by the allocate action
+            if (cfreq[id] == 0) continue;  // only classes that have pending pods are ever queried by the allocate action
             if (!admissible || (int)classes.size() >= KAI_CMAX) { all_tracked = 0; continue; }
             ClassRec cr; std::memset(&cr, 0, sizeof cr);
             for (int r = 0; r < KAI_MAX_RES; r++) cr.req[r] = k.req[r];
             cr.pod_class = k.pc; cr.cpu_only = cpu_only;
             bool be = !(k.req[KAI_RES_GPU] > 0.01) && !(k.req[KAI_RES_CPU] >= 10.0 || k.req[KAI_RES_MEM] >= 10.0 * 1024 * 1024);
-            for (int r = KAI_RES_PODS; r < R; r++) if (k.req[r] >= 10.0) be = false;
+            for (int r = KAI_RES_PODS; r < KAI_MAX_RES; r++) if (k.req[r] >= 10.0) be = false;
             cr.best_effort = be; cr.r_place = cpu_only ? KAI_RES_CPU : KAI_RES_GPU; cr.strategy = cpu_only ? cfg.cpu_strategy : cfg.gpu_strategy;
             remap[id] = (int)classes.size(); classes.push_back(cr);
         }
-        parallel_chunks((size_t)P, [&](int, size_t p0, size_t p1) { for (size_t p = p0; p < p1; p++) pod_scls[p] = (sh && sh[p]) ? -1 : remap[(size_t)pod_cls[p]]; });
-        int NB = (N + KAI_BLOCK - 1) / KAI_BLOCK, NSB = (NB + 63) / 64;
-        if (NSB > KAI_NSB_MAX) { classes.clear(); par_fill(pod_scls, (size_t)P, -1); all_tracked = 0; }  // beyond the LDS level: brute force
+        if (nsb_over) { classes.clear(); std::fill(remap.begin(), remap.end(), -1); all_tracked = 0; }
     }
 };
 

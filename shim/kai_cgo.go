@@ -434,6 +434,7 @@ type packParams struct{ schedulerName, gpuWorkerLabel, cpuWorkerLabel string }
 type plugin struct {
 	params packParams
 	pack   *packedSnapshot
+	prev   *packedSnapshot // the last cycle's pack, whose session stays open: the next cycle sends a delta against it (kai_session_update)
 }
 
 var current *plugin
@@ -445,14 +446,161 @@ func New(args framework.PluginArguments) framework.Plugin {
 func (p *plugin) Name() string { return "gpucore" }
 func (p *plugin) OnSessionOpen(ssn *framework.Session) { // framework/interface.go:49-55
 	p.pack = packSnapshot(ssn, p.params)
+	// Between two cycles most of the snapshot stays the same: when the new pack differs from the last one only in pod status / node / shared-GPU group
+	// and node flags / allocatable, the open session takes a delta (cost in proportion to the change) instead of the whole snapshot.
+	if p.prev != nil && !p.prev.fallback && sameStructure(p.prev, p.pack) {
+		d := packDelta(p.prev, p.pack)
+		rc := C.kai_session_update(core, &d.delta)
+		d.free()
+		if rc == 0 {
+			p.dropPrev()
+			return
+		}
+	}
+	p.dropPrev()
 	if rc := C.kai_session_open(core, &p.pack.soa); rc != 0 {
 		p.pack.fallback = true // e.g. KAI_ERR_UNSUPPORTED: leave this cycle to the Go actions
 	}
 }
 func (p *plugin) OnSessionClose(*framework.Session) {
-	C.kai_session_close(core)
-	p.pack.free()
+	// the session stays open for the next cycle's delta; kai_session_open / kai_session_update of that cycle replace it
+	if p.pack.fallback {
+		C.kai_session_close(core)
+		p.pack.free()
+	} else {
+		p.prev = p.pack
+	}
 	p.pack = nil
+}
+func (p *plugin) dropPrev() {
+	if p.prev != nil {
+		p.prev.free()
+		p.prev = nil
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ session delta (kai_session_update)
+type packedDelta struct {
+	delta  C.kai_session_delta
+	allocs []unsafe.Pointer
+}
+
+func (d *packedDelta) free() {
+	for _, a := range d.allocs {
+		C.free(a)
+	}
+	d.allocs = nil
+}
+
+func bytesOf[T any](p *T, n int) []byte {
+	if p == nil || n <= 0 {
+		return nil
+	}
+	var zero T
+	return unsafe.Slice((*byte)(unsafe.Pointer(p)), n*int(unsafe.Sizeof(zero)))
+}
+
+// the same snapshot structure: the same counts and every array except pod status / node / shared-GPU group and node flags / allocatable byte for byte equal
+func sameStructure(a, b *packedSnapshot) bool {
+	x, y := &a.soa, &b.soa
+	if x.n_res != y.n_res || x.n_nodes != y.n_nodes || x.n_pods != y.n_pods || x.n_podsets != y.n_podsets || x.n_jobs != y.n_jobs || x.n_queues != y.n_queues ||
+		x.n_pod_classes != y.n_pod_classes || x.n_node_classes != y.n_node_classes || x.n_topologies != y.n_topologies || x.n_topo_levels != y.n_topo_levels ||
+		x.n_domains != y.n_domains || x.n_groups != y.n_groups {
+		return false
+	}
+	N, P, S, J, Q, R := int(x.n_nodes), int(x.n_pods), int(x.n_podsets), int(x.n_jobs), int(x.n_queues), int(x.n_res)
+	Tn, TL, D, G := int(x.n_topologies), int(x.n_topo_levels), int(x.n_domains), int(x.n_groups)
+	eq := func(u, v []byte) bool { return string(u) == string(v) }
+	same := eq(bytesOf(x.node_gpu_count, N), bytesOf(y.node_gpu_count, N)) && eq(bytesOf(x.node_name_rank, N), bytesOf(y.node_name_rank, N)) &&
+		eq(bytesOf(x.node_class, N), bytesOf(y.node_class, N)) && eq(bytesOf(x.node_gpu_memory, N), bytesOf(y.node_gpu_memory, N)) &&
+		eq(bytesOf(x.pod_req, R*P), bytesOf(y.pod_req, R*P)) && eq(bytesOf(x.pod_job, P), bytesOf(y.pod_job, P)) && eq(bytesOf(x.pod_podset, P), bytesOf(y.pod_podset, P)) &&
+		eq(bytesOf(x.pod_flags, P), bytesOf(y.pod_flags, P)) && eq(bytesOf(x.pod_task_priority, P), bytesOf(y.pod_task_priority, P)) &&
+		eq(bytesOf(x.pod_created_ns, P), bytesOf(y.pod_created_ns, P)) && eq(bytesOf(x.pod_uid_rank, P), bytesOf(y.pod_uid_rank, P)) &&
+		eq(bytesOf(x.pod_class, P), bytesOf(y.pod_class, P)) && eq(bytesOf(x.pod_nominated_node, P), bytesOf(y.pod_nominated_node, P)) &&
+		eq(bytesOf(x.pod_gpu_portion, P), bytesOf(y.pod_gpu_portion, P)) && eq(bytesOf(x.pod_gpu_memory, P), bytesOf(y.pod_gpu_memory, P)) &&
+		eq(bytesOf(x.podset_job, S), bytesOf(y.podset_job, S)) && eq(bytesOf(x.podset_min_available, S), bytesOf(y.podset_min_available, S)) &&
+		eq(bytesOf(x.podset_name_rank, S), bytesOf(y.podset_name_rank, S)) &&
+		eq(bytesOf(x.job_queue, J), bytesOf(y.job_queue, J)) && eq(bytesOf(x.job_priority, J), bytesOf(y.job_priority, J)) &&
+		eq(bytesOf(x.job_preemptible, J), bytesOf(y.job_preemptible, J)) && eq(bytesOf(x.job_created_ns, J), bytesOf(y.job_created_ns, J)) &&
+		eq(bytesOf(x.job_uid_rank, J), bytesOf(y.job_uid_rank, J)) && eq(bytesOf(x.job_first_pod, J), bytesOf(y.job_first_pod, J)) &&
+		eq(bytesOf(x.job_n_pods, J), bytesOf(y.job_n_pods, J)) && eq(bytesOf(x.job_first_podset, J), bytesOf(y.job_first_podset, J)) &&
+		eq(bytesOf(x.job_n_podsets, J), bytesOf(y.job_n_podsets, J)) && eq(bytesOf(x.job_signature, J), bytesOf(y.job_signature, J)) &&
+		eq(bytesOf(x.job_last_start_ns, J), bytesOf(y.job_last_start_ns, J)) && eq(bytesOf(x.job_root_group, J), bytesOf(y.job_root_group, J)) &&
+		eq(bytesOf(x.queue_parent, Q), bytesOf(y.queue_parent, Q)) && eq(bytesOf(x.queue_priority, Q), bytesOf(y.queue_priority, Q)) &&
+		eq(bytesOf(x.queue_created_ns, Q), bytesOf(y.queue_created_ns, Q)) && eq(bytesOf(x.queue_uid_rank, Q), bytesOf(y.queue_uid_rank, Q)) &&
+		eq(bytesOf(x.queue_deserved, 3*Q), bytesOf(y.queue_deserved, 3*Q)) && eq(bytesOf(x.queue_limit, 3*Q), bytesOf(y.queue_limit, 3*Q)) &&
+		eq(bytesOf(x.queue_oqw, 3*Q), bytesOf(y.queue_oqw, 3*Q)) && eq(bytesOf(x.queue_usage, 3*Q), bytesOf(y.queue_usage, 3*Q)) &&
+		eq(bytesOf(x.queue_preempt_min_runtime_ns, Q), bytesOf(y.queue_preempt_min_runtime_ns, Q)) && eq(bytesOf(x.queue_reclaim_min_runtime_ns, Q), bytesOf(y.queue_reclaim_min_runtime_ns, Q)) &&
+		eq(bytesOf(x.class_fit, int(x.n_pod_classes)*int(x.n_node_classes)), bytesOf(y.class_fit, int(y.n_pod_classes)*int(y.n_node_classes))) &&
+		eq(bytesOf(x.topo_level_off, Tn+1), bytesOf(y.topo_level_off, Tn+1)) && eq(bytesOf(x.node_domain, TL*N), bytesOf(y.node_domain, TL*N)) &&
+		eq(bytesOf(x.domain_level, D), bytesOf(y.domain_level, D)) && eq(bytesOf(x.domain_parent, D), bytesOf(y.domain_parent, D)) && eq(bytesOf(x.domain_id_rank, D), bytesOf(y.domain_id_rank, D)) &&
+		eq(bytesOf(x.group_job, G), bytesOf(y.group_job, G)) && eq(bytesOf(x.group_parent, G), bytesOf(y.group_parent, G)) && eq(bytesOf(x.group_name_rank, G), bytesOf(y.group_name_rank, G)) &&
+		eq(bytesOf(x.group_topology, G), bytesOf(y.group_topology, G)) && eq(bytesOf(x.group_required_level, G), bytesOf(y.group_required_level, G)) &&
+		eq(bytesOf(x.group_preferred_level, G), bytesOf(y.group_preferred_level, G)) &&
+		eq(bytesOf(x.podset_group, S), bytesOf(y.podset_group, S)) && eq(bytesOf(x.podset_topology, S), bytesOf(y.podset_topology, S)) &&
+		eq(bytesOf(x.podset_required_level, S), bytesOf(y.podset_required_level, S)) && eq(bytesOf(x.podset_preferred_level, S), bytesOf(y.podset_preferred_level, S)) &&
+		eq(bytesOf(x.res_mig_gpus, R), bytesOf(y.res_mig_gpus, R)) && eq(bytesOf(x.res_mig_memory, R), bytesOf(y.res_mig_memory, R))
+	// an optional array present in one pack and absent in the other is a structural change too (the pod_gpu_group array travels in the delta)
+	return same && (x.pod_gpu_portion == nil) == (y.pod_gpu_portion == nil) && (x.pod_gpu_memory == nil) == (y.pod_gpu_memory == nil) &&
+		(x.node_gpu_memory == nil) == (y.node_gpu_memory == nil) && (x.job_signature == nil) == (y.job_signature == nil)
+}
+
+// the pods and nodes whose status / node / group or flags / allocatable differ between the two packs, in C memory
+func packDelta(a, b *packedSnapshot) *packedDelta {
+	x, y := &a.soa, &b.soa
+	N, P, R := int(y.n_nodes), int(y.n_pods), int(y.n_res)
+	xs, ys := unsafe.Slice(x.pod_status, P), unsafe.Slice(y.pod_status, P)
+	xn, yn := unsafe.Slice(x.pod_node, P), unsafe.Slice(y.pod_node, P)
+	group := func(s *C.kai_snapshot_soa, i int) C.int32_t {
+		if s.pod_gpu_group == nil {
+			return -1
+		}
+		return unsafe.Slice(s.pod_gpu_group, P)[i]
+	}
+	var pods []int
+	for i := 0; i < P; i++ {
+		if xs[i] != ys[i] || xn[i] != yn[i] || group(x, i) != group(y, i) {
+			pods = append(pods, i)
+		}
+	}
+	xf, yf := unsafe.Slice(x.node_flags, N), unsafe.Slice(y.node_flags, N)
+	xa, ya := unsafe.Slice(x.node_allocatable, R*N), unsafe.Slice(y.node_allocatable, R*N)
+	var nodes []int
+	for n := 0; n < N; n++ {
+		diff := xf[n] != yf[n]
+		for r := 0; r < R && !diff; r++ {
+			diff = xa[r*N+n] != ya[r*N+n]
+		}
+		if diff {
+			nodes = append(nodes, n)
+		}
+	}
+	d := &packedDelta{}
+	alloc := func(bytes int) unsafe.Pointer { m := C.malloc(C.size_t(max(bytes, 1))); d.allocs = append(d.allocs, m); return m }
+	np, nn := len(pods), len(nodes)
+	pod := unsafe.Slice((*C.int32_t)(alloc(4*np)), max(np, 1))
+	st := unsafe.Slice((*C.int32_t)(alloc(4*np)), max(np, 1))
+	nd := unsafe.Slice((*C.int32_t)(alloc(4*np)), max(np, 1))
+	gr := unsafe.Slice((*C.int32_t)(alloc(4*np)), max(np, 1))
+	for k, i := range pods {
+		pod[k], st[k], nd[k], gr[k] = C.int32_t(i), ys[i], yn[i], group(y, i)
+	}
+	node := unsafe.Slice((*C.int32_t)(alloc(4*nn)), max(nn, 1))
+	fl := unsafe.Slice((*C.uint32_t)(alloc(4*nn)), max(nn, 1))
+	al := unsafe.Slice((*C.double)(alloc(8*R*nn)), max(R*nn, 1))
+	for k, n := range nodes {
+		node[k], fl[k] = C.int32_t(n), yf[n]
+		for r := 0; r < R; r++ {
+			al[r*nn+k] = ya[r*N+n]
+		}
+	}
+	d.delta.version = C.KAI_DELTA_VERSION
+	d.delta.n_pods, d.delta.pod, d.delta.pod_status, d.delta.pod_node = C.int32_t(np), &pod[0], &st[0], &nd[0]
+	if y.pod_gpu_group != nil || x.pod_gpu_group != nil {
+		d.delta.pod_gpu_group = &gr[0]
+	}
+	d.delta.n_nodes, d.delta.node, d.delta.node_flags, d.delta.node_allocatable = C.int32_t(nn), &node[0], &fl[0], &al[0]
+	return d
 }
 
 // ------------------------------------------------------------------------------------------------ framework.Action
