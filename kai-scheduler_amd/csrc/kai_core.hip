@@ -23,9 +23,21 @@
 #include "kai_victim_shard.hpp"
 #include "kai_delta.hpp"
 #include <map>
+#include <mutex>
 #include <thread>
 
 using namespace kai;
+
+// The dynamic-LDS ceiling of a kernel (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the process and the device, not to a handle: a second handle with a smaller cluster
+// must not lower it under the first handle's next launch.  So the mark is kept per device for the whole process and only ever rises.  which: 0 k_fill_buckets, 1 k_fill_counts, 2 k_fill_levels.
+static bool fill_dyn_raise(int device, int which, const void* kernel, size_t dyn) {
+    static std::mutex mu; static std::map<int, size_t> mark[3];
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& m = mark[which][device];
+    if (dyn <= m) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) return false;
+    m = dyn; return true;
+}
 
 struct kai_core {
     kai_config cfg{};
@@ -61,7 +73,6 @@ struct kai_core {
     hipEvent_t bev[4] = {nullptr, nullptr, nullptr, nullptr};
     // rounds without the host (kai_batch_driver.hpp): per slot the round's phase events (plan start, fill start, fill end, apply end), the event behind its RoundCtl copy, the pinned copy
     hipEvent_t rev[KB_ROUND_SLOTS][5] = {}; unsigned char* rpin = nullptr; bool rev_ready = false;
-    size_t fill_dyn_set[3] = {0, 0, 0};  // dynamic-LDS ceiling already set for k_fill_buckets / k_fill_counts / k_fill_levels (hipFuncSetAttribute is per process and device: once, not once per action)
     double batch_plan_ms = 0, batch_fill_ms = 0, batch_apply_ms = 0;
     // victim actions on several workgroups (kai_engine_solver.inc solve_partial_multi): every array a KaiCtx field points to, so that each workgroup gets a replica
     struct AllocRec { size_t field_off; char* base; size_t bytes; };
@@ -314,19 +325,19 @@ struct DevLauncher {
     }
     void bucket_build(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_bucket_build, dim3(g), dim3(b), 0, core->stream, c); }
     void fill_counts(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {
-        if (dyn > core->fill_dyn_set[1]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_counts), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) rc = KAI_ERR_HIP; else core->fill_dyn_set[1] = dyn; }
+        if (!fill_dyn_raise(core->device, 1, reinterpret_cast<const void*>(k_fill_counts), dyn)) rc = KAI_ERR_HIP;
         if (rp.mode == 0) (void)hipEventRecord(ev(1), core->stream);
         hipLaunchKernelGGL(k_fill_counts, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
         if (rp.mode != 1) (void)hipEventRecord(ev(2), core->stream);
     }
     void fill_levels(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {
-        if (dyn > core->fill_dyn_set[2]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_levels), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) rc = KAI_ERR_HIP; else core->fill_dyn_set[2] = dyn; }
+        if (!fill_dyn_raise(core->device, 2, reinterpret_cast<const void*>(k_fill_levels), dyn)) rc = KAI_ERR_HIP;
         if (rp.mode == 0) (void)hipEventRecord(ev(1), core->stream);
         hipLaunchKernelGGL(k_fill_levels, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
         if (rp.mode != 1) (void)hipEventRecord(ev(2), core->stream);
     }
     void fill_buckets(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {
-        if (dyn > core->fill_dyn_set[0]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_buckets), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) rc = KAI_ERR_HIP; else core->fill_dyn_set[0] = dyn; }
+        if (!fill_dyn_raise(core->device, 0, reinterpret_cast<const void*>(k_fill_buckets), dyn)) rc = KAI_ERR_HIP;
         if (rp.mode == 0) (void)hipEventRecord(ev(1), core->stream);
         hipLaunchKernelGGL(k_fill_buckets, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
         if (rp.mode != 1) (void)hipEventRecord(ev(2), core->stream);

@@ -10,6 +10,8 @@
 //     non-empty level >= q, whole nodes per step — and its commands are published when its last task has found a level; a gang that runs out of levels is rolled back (counts, mask
 //     and ring position: three registers) having booked the tasks it placed + 1 decisions, exactly what the capacity rule of kai_fill_counts.hpp books.  So this wavefront keeps no
 //     capacities at all.  Outcomes, Statement numbers and operation offsets of a stretch come out of one ballot and one prefix sum at its end.  A command is 8 bytes.
+//     This wavefront's chain of dependent instructions is the kernel's length, so the walk is written for the instruction stream it compiles to: the usual gang
+//     — one class, 1 .. KFL_SHORT tasks — runs through ≈ 100 instructions and two branches, everything but the counts in scalar registers.
 //   * Wavefronts 1 .. L, the set workers: level g belongs to wavefront g, alone.  Its words, its two summaries and its first node are that wavefront's uniform state (the word that
 //     holds the first node is cached in registers: removing the level's first node — what every command does — reads nothing from LDS while that word lasts).  A worker looks at 64
 //     commands at a time, one per lane, and walks the ones that name its level: as the SOURCE it removes the level's first k nodes, writes the tasks' nodes and hands (word, mask) to
@@ -17,7 +19,7 @@
 //     insertions in command order; nodes only move DOWN the levels, so the wait-for graph has no cycle (a producer waits only for a consumer that is behind it; the worker that is
 //     furthest behind waits for nobody).
 //   * Wavefront L + 1, the bookkeeper: what a dead gang books is cap + 1 decisions with the capacity cap[q] = Σ_g (g / q)·cnt[g] AT ITS TURN.  The bookkeeper replays the command stream
-//     (lane q − 1 keeps cap[q]: two table look-ups and a multiply-add per command), finds a command's job by its task range, and books the dead gangs between two walked jobs with one
+//     (lane q − 1 keeps cap[q]: two table look-ups and a multiply-add per command), is told a command's job by the command and a stretch's start by its marker, and books the dead gangs between two walked jobs with one
 //     population count — off the chain the other wavefronts wait for.
 //
 // Results are identical to k_fill_counts / k_fill_buckets (and through them to the oracle): tests/test_batch_path.py and tests/test_gpu_parity.py run the fills against each other, the
@@ -32,8 +34,10 @@ constexpr int KFL_LMAX = 8;                                // levels = worker wa
 constexpr int KFL_RING = 4096;                             // commands the ring holds (a gang, <= KB_PLACED_MAX commands, is written in full before it is published)
 constexpr int KFL_XR = 32;                                 // entries of a hand-over ring
 constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": the stretch reserves its commands' room in the ring up front
+constexpr int KFL_JOB_SHIFT = 23;                          // a command's bits 23-28: its job's index within the stretch (or-ed in by the counting machine: kfl_cmd knows nothing of it)
 constexpr int KFL_PAIRS = KFL_LMAX * (KFL_LMAX - 1) / 2;   // (source level g, target level g2 < g)
 // a command, 8 bytes: bits 0-3 g, 4-7 g2, 8-11 per, 12-22 k | the upper word: tbase — the first k nodes of level g take `per` tasks each and move to level g2 (0: no level); their tasks are t_node[tbase ..)
+// A word with g = 0 is no command but a stretch's MARKER: the counting machine writes one in front of every stretch's commands.
 KW_BODY uint64_t kfl_cmd(int g, int g2, int k, int per, int tbase) { return (uint64_t)((uint32_t)g | ((uint32_t)g2 << 4) | ((uint32_t)per << 8) | ((uint32_t)k << 12)) | ((uint64_t)(uint32_t)tbase << 32); }
 struct FlMove { uint64_t mask; int32_t w; int32_t seq; };  // the nodes `mask` of word w (bit 30 of w: the command's last entry); seq = the entry's number in its ring + 1, stored last (release)
 struct FlLds {
@@ -55,6 +59,8 @@ KW_BODY int kfl_div(int a, int b) {
 // uniform accesses of a worker to its own level's LDS words: every lane reads the same address and takes lane 0's value (a scalar from then on); lane 0 writes
 KW_BODY uint64_t kfl_read(KW_LDS_PTR(uint64_t) p) { return kw::bcast(*p, 0); }
 KW_BODY void kfl_write(KW_LDS_PTR(uint64_t) p, uint64_t v) { if (kw::lane() == 0) *p = v; }
+// a counter another wavefront publishes (acquire), as a scalar: every lane reads the same address
+KW_BODY int kfl_load(const int32_t* p) { return kw::uni(kw::lds_load_acq(p)); }
 // one stretch of 64 planned jobs as the counting machine and the bookkeeper both see it: lane j holds job j
 struct FlStretch { int flag, first, nt, q; bool valid, is_def; uint64_t defm, todo; };
 // lane q − 1: the quotients g / q for g = 1 .. 8, four bits each (bits 4(g − 1) ..)
@@ -96,17 +102,22 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     }
     kw::sync();
     const int V = rp.mode != 1 ? b.q_valid[c.Q] : 0;  // mode 1: dead classes only (before the first plan)
-    const int wave = tid >> 6;
+    const int wave = kw::uni(tid >> 6);  // (the compiler takes anything computed from the thread's number for different in every lane: told otherwise, a wavefront's role, its level and its tests sit on the scalar unit)
     if (wave == 0) {
         // ------------------------------------------------------------------ wavefront 0: the counting machine.
-        // lane l: cnt = nodes of level l + 1.  lane q − 1: tab = the quotients g / q.  lane k: qk = devices class k asks for.
+        // lane l: cnt = nodes of level l + 1 (lane 63: nodes that left for no level, see KFL_EVENT).  lane q − 1: tab = the quotients g / q.  lane k: qk = devices class k asks for.
+        // lane b − 1: invq = ceil(2^15 / b), the table of kfl_div (b = 1: a·2^15 >> 15 = a, so the step divides without asking whether it has to).
+#ifdef KFL_PRIO
+        kw::set_prio<KFL_PRIO>();  // (an experiment on placement, DESIGN.md 5.2d: no gain measured, off in the product)
+#endif
         int cnt = lane < v.LV ? L.cnt0[lane] : 0;
         const bool act = lane < C;
         const int qk = act ? (int)c.cls[lane].req[KAI_RES_GPU] : 0x7fffffff;
         const uint32_t tab = kfl_tab(lane, v.LV);
+        const int invq = (int)(((lane < 4 ? 0x2000'2AAB'4000'8000ull : 0x1000'124A'1556'199Aull) >> (16 * (lane & 3))) & 0xffff);
         uint32_t nz = (uint32_t)kw::ballot(cnt > 0);  // bit l: level l + 1 holds a node
         int decisions = 0, attempted = 0, committed = 0, rollbacks = 0, ops = 0, n_done = rp.start, mismatch = 0;
-        int wp = 0, tail_seen = 0, pub = 0;  // commands written / the slowest reader's progress as last read / commands published (per 64 commands and at the end of a stretch)
+        int wp = 0, tail_seen = 0, pub = 0, n_mark = 0;  // commands written (the stretches' markers, n_mark, among them) / the slowest reader's progress as last read / commands published (per 64 commands and at the end of a stretch)
         int64_t a_wait = 0;               // cycles this wavefront waited for room in the ring
 #ifdef KFL_PROF
         int64_t pc[5] = {0, 0, 0, 0, 0}; int64_t pt = kw::clock();
@@ -120,10 +131,41 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         #define KFL_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (qc) + __builtin_ctz(nz >> ((qc) - 1)) : 0)
         // room for n more commands in the ring (a gang stays unpublished until its last task has found a level)
         #define KFL_ROOM(n) do { if (wp - tail_seen > KFL_RING - (n)) { kw::lds_store_rel(&L.head, wp); pub = wp; const int64_t w0 = kw::clock(); while (wp - tail_seen > KFL_RING - (n)) { tail_seen = tails_min(); if (wp - tail_seen > KFL_RING - (n)) kw::relax(); } a_wait += kw::clock() - w0; } } while (0)
-        // lane 0 writes the command, the other lanes a copy into a slot of their own: one store, no branch
-        #define KFL_EMIT(g_, g2_, k_, per_, tb_) do { KW_LDS_PTR(uint64_t) sl_ = lane == 0 ? (KW_LDS_PTR(uint64_t))&L.ring[wp & (KFL_RING - 1)] : (KW_LDS_PTR(uint64_t))&L.dummy[lane]; *sl_ = kfl_cmd(g_, g2_, k_, per_, tb_); wp++; } while (0)
-        // k nodes leave level g for level g2 (0: none): the counts and the non-empty mask
-        #define KFL_EVENT(g_, g2_, k_) do { cnt -= lane == (g_) - 1 ? (k_) : 0; cnt += lane == (g2_) - 1 ? (k_) : 0; nz = (uint32_t)kw::ballot(cnt > 0); } while (0)
+        // lane 0 writes the command, the other lanes a copy into a slot of their own: one store, no branch.  jbits: the job's index within its stretch at bits 23-28 (for the bookkeeper)
+        #define KFL_EMIT(g_, g2_, k_, per_, tb_) do { KW_LDS_PTR(uint64_t) sl_ = lane == 0 ? (KW_LDS_PTR(uint64_t))&L.ring[wp & (KFL_RING - 1)] : (KW_LDS_PTR(uint64_t))&L.dummy[lane]; *sl_ = kfl_cmd(g_, g2_, k_, per_, tb_) | jbits; wp++; } while (0)
+        // k nodes leave level g, which holds cg >= k, for level g2 (0: none): two lanes of the counts are written, two bits of the non-empty mask change (bit g − 1 goes when the level
+        // is emptied, bit g2 − 1 comes) — all of it on the scalar unit.  Nodes that leave for no level are counted in lane 63, which nobody reads; a step without a level (g = 0,
+        // k = 0, g2 <= 0) changes no lane, and the gang it belongs to is rolled back.
+        // (Truth values are kept as the integers 0 / 1 taken from a sign bit, each used once: a comparison whose result is both selected on and added up comes back from the
+        // compiler as a lane mask, a vector select and a read back into a scalar register — 30 cycles.)
+        #define KFL_EVENT(g_, g2_, k_, cg_) do { const int e_g = (g_), e_g2 = (g2_), e_k = (k_), e_cg = (cg_); \
+            cnt = kw::writelane(cnt, e_cg - e_k, (e_g - 1) & 63); \
+            const uint32_t e_in = e_g2 >= 1 ? 1u << ((e_g2 - 1) & 31) : 0u, e_out = (uint32_t)(e_cg - e_k - 1) >> 31;  /* bit g2 - 1 if g2 >= 1: the target level gains nodes | cg == k: the source level is emptied */ \
+            cnt = kw::writelane(cnt, kw::bcast(cnt, (e_g2 - 1) & 63) + e_k, (e_g2 - 1) & 63); \
+            nz = (nz & ~(e_out << ((e_g - 1) & 31))) | e_in; } while (0)
+        // one step of a gang of ONE class, whole nodes: the lowest non-empty level g >= q holds r = g / q of its tasks per node; the first k nodes of it take r tasks each and move to
+        // level g mod q, a remainder of fewer than r tasks goes to one node, which then stays at level g − rem·q.  No level: the step moves nothing and the gang has failed (it writes
+        // a slot that stays unpublished: whatever its fields hold).
+        #define KFL_STEP() do { \
+            const int g = KFL_LEVEL_FOR(qc), gm1 = g - 1; \
+            fail = (int)((uint32_t)gm1 >> 31);  /* g == 0 */ \
+            int r = (int)((tq >> ((4 * g - 4) & 31)) & 15u); r = r > 1 ? r : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
+            const int rem = nt - placed; \
+            const int kq = (int)(((uint32_t)rem * (uint32_t)kw::bcast(invq, r - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
+            const int cg = kw::bcast(cnt, gm1 & 63); \
+            int k = kq < cg ? kq : cg; k = k > 1 ? k : 1; k &= fail - 1;  /* min(kq, nodes of the level), at least the one node; no level: nothing moves */ \
+            const int per = r < rem ? r : rem, g2 = g - per * qc; \
+            KFL_EMIT(g, g2, k, per, first + placed); \
+            KFL_EVENT(g, g2, k, cg); \
+            placed += k * per; } while (0)
+        // a gang's end: its outcome bit, what it booked (every task placed is a decision — a gang that fits places them all —, a gang that found no node for its next task booked that
+        // one too), Statement.Rollback (nothing was published: the counts, the mask and the ring position, the counts being the one vector select), and whether it ended as predicted
+        #define KFL_GANG_END() \
+            okm |= (uint64_t)(uint32_t)(1 - fail) << jj; \
+            decisions += placed + fail; rollbacks += 2 * fail; \
+            cnt = fail ? cnt_s : cnt; nz = fail ? nz_s : nz; wp = fail ? wp_s : wp; \
+            const int mism = (int)((uint32_t)(flag - 1) >> 31) ^ fail ^ 1;  /* (flag == BF_OK) != ok — the job ended differently from its prediction: it is the round's last */ \
+            mismatch |= mism; last_jj = jj
         // the 64 jobs of a stretch: one per lane; the NEXT stretch's loads are issued before this stretch is walked
         int nx_flag = 0, nx_first = 0, nx_nt = 0, nx_ucls = 0;
         if (V > rp.start) { const int gc = rp.start + lane < V ? rp.start + lane : V - 1; nx_flag = b.g_flag[gc]; nx_first = b.g_first[gc]; nx_nt = b.g_nt[gc]; nx_ucls = b.g_ucls[gc]; }
@@ -137,72 +179,84 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
             int capq = 0;  // lane q − 1: the tasks that ask for q devices the levels hold at the stretch's start
             for (int g = 1; g <= v.LV; g++) capq += kfl_quot(tab, g) * kw::bcast(cnt, g - 1);
             kfl_classify(s, my_ucls, qk, capq);
-            // a job's parameters in one word: flag (2 bits), devices (5 bits), tasks (up to KB_PLACED_MAX: 11 bits), bit 18: the long way (several classes, or more tasks than the
-            // stretch's reservation in the ring covers)
-            const int my_pack = s.flag | (s.q << 2) | (s.nt << 7) | ((s.q == 0 || s.nt > KFL_SHORT) ? 1 << 18 : 0);
+            // a job's parameters in one word: flag (2 bits), devices (5 bits), tasks (up to KB_PLACED_MAX: 11 bits), bit 18: the long way (several classes, more tasks than the
+            // stretch's reservation in the ring covers, or none at all: the short way takes its first step without asking)
+            const int my_pack = s.flag | (s.q << 2) | (s.nt << 7) | ((s.q == 0 || s.nt > KFL_SHORT || s.nt < 1) ? 1 << 18 : 0);
             const uint32_t my_tq = kw::shfl(tab, s.q >= 1 ? s.q - 1 : 63);  // the quotients g / q of the job's request
+            const uint64_t longm = kw::ballot((my_pack >> 18) != 0);
             uint64_t todo = s.todo, okm = 0;  // okm: jobs of this stretch that committed
             int n_out = jn, last_jj = 0;
             attempted += jn; n_done = base + jn;
-            KFL_ROOM(64 * KFL_SHORT);  // room for every short gang of the stretch: no check per gang
+            KFL_ROOM(64 * KFL_SHORT + 1);  // room for the stretch's marker and every short gang of it: no check per gang
 #if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(my_tq), "v"(my_pack) : "memory");  // the stretch's shuffles have landed: the walk below never waits on the LDS counter (its own command stores stay in flight)
 #endif
+            // the stretch's marker, in ring order in front of its commands: the bookkeeper enters the stretch there (no worker looks at it: it names no level)
+            { KW_LDS_PTR(uint64_t) sl_ = lane == 0 ? (KW_LDS_PTR(uint64_t))&L.ring[wp & (KFL_RING - 1)] : (KW_LDS_PTR(uint64_t))&L.dummy[lane]; *sl_ = 0; wp++; n_mark++; }
             KFL_T(0);
-            // (a conditional branch costs this wavefront ≈ 20 cycles whether it is taken or not, a scalar instruction ≈ 5 — tools/micro/issue_rate.hip: the walk below selects instead of
-            // branching wherever both sides are a few instructions)
+            // (a conditional branch costs this wavefront 22 - 31 cycles whether it is taken or not, a scalar instruction 5 - 6, a dependent vector instruction 7, a vector compare that
+            // feeds the scalar unit 30 — tools/micro/issue_rate.hip.  So the usual gang — one class, 1 .. KFL_SHORT tasks — runs straight through: the short gangs in front of the next
+            // long one are walked by a loop that holds nothing else, its first step without a test, one rarely taken branch for further steps, and ONE test at its end for "more to
+            // walk, nothing to publish, predicted right".  Everything but the counts lives in scalar registers.)
             while (todo) {
-                const int jj = __builtin_ctzll(todo); todo &= todo - 1;
-                const int pack = kw::bcast(my_pack, jj), first = kw::bcast(s.first, jj);
-                const uint32_t tq = kw::bcast(my_tq, jj);
-                const int flag = pack & 3, qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
-                KFL_T(1);
-                // the gang on the counts; its commands stay unpublished until its last task has found a level
-                const int cnt_s = cnt, wp_s = wp; const uint32_t nz_s = nz;
-                int placed = 0; bool fail = false;
-                if (pack >> 18) {
+                const uint64_t lm = todo & longm;
+                const uint64_t below = lm ? (lm & (0 - lm)) - 1 : ~0ull;  // the jobs in front of the next long one
+                uint64_t hot = todo & below;
+                todo &= ~below;
+                if (hot) {
+                    uint64_t go;
+                    do {
+                        const int jj = __builtin_ctzll(hot); hot &= hot - 1;
+                        const int pack = kw::bcast(my_pack, jj), first = kw::bcast(s.first, jj);
+                        const uint32_t tq = kw::bcast(my_tq, jj);
+                        const int flag = pack & 3, qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
+                        const uint64_t jbits = (uint64_t)((uint32_t)jj << KFL_JOB_SHIFT);
+                        KFL_T(1);
+                        // the gang on the counts; its commands stay unpublished until its last task has found a level
+                        const int cnt_s = cnt, wp_s = wp; const uint32_t nz_s = nz;
+                        int placed = 0, fail;
+                        KFL_STEP();
+                        while (__builtin_expect((int)((placed < nt) & (fail == 0)), 0)) KFL_STEP();
+                        KFL_T(2);
+                        KFL_GANG_END();
+                        go = hot & (uint64_t)((int64_t)(int32_t)kw::uni((int)(((uint32_t)mism | ((uint32_t)(wp - pub) >> 6)) - 1u)) >> 63);  // (wp >= pub: the difference reaches 64 when bit 6 or a higher one is set)
+                        KFL_T(3);
+                    } while (go);
+                }
+                todo |= hot;
+                if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
+                if (mismatch) break;
+                if (!hot && lm) {
+                    // the long way: a gang of several classes task by task, a gang of one class with more tasks than the stretch reserved room for (or none)
+                    const int jj = __builtin_ctzll(todo); todo &= todo - 1;
+                    const int pack = kw::bcast(my_pack, jj), first = kw::bcast(s.first, jj);
+                    const uint32_t tq = kw::bcast(my_tq, jj);
+                    const int flag = pack & 3, qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
+                    const uint64_t jbits = (uint64_t)((uint32_t)jj << KFL_JOB_SHIFT);
+                    KFL_T(1);
+                    const int cnt_s = cnt, wp_s = wp; const uint32_t nz_s = nz;
+                    int placed = 0, fail = 0;
                     KFL_ROOM(nt + 64 * KFL_SHORT);
                     if (!qc) {
-                        // a gang of several scan classes: task by task
                         for (int tb = 0; tb < nt && !fail; tb += 64) {
                             const int my_cls = tb + lane < nt ? b.t_cls[first + tb + lane] : 0;
                             const int tc = nt - tb < 64 ? nt - tb : 64;
                             for (int ti = 0; ti < tc; ti++) {
                                 const int q1 = kw::bcast(qk, kw::bcast(my_cls, ti));
                                 const int g = q1 <= 31 ? KFL_LEVEL_FOR(q1) : 0;
-                                if (!g) { fail = true; break; }
+                                if (!g) { fail = 1; break; }
                                 KFL_EMIT(g, g - q1, 1, 1, first + placed);
-                                KFL_EVENT(g, g - q1, 1);
+                                KFL_EVENT(g, g - q1, 1, kw::bcast(cnt, g - 1));
                                 placed++;
                             }
                         }
-                    }
+                    } else while ((placed < nt) & (fail == 0)) KFL_STEP();
+                    KFL_T(2);
+                    KFL_GANG_END();
+                    if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
+                    KFL_T(3);
+                    if (mism) break;
                 }
-                // a gang of ONE class: whole nodes per step.  The lowest non-empty level g >= q holds r = g / q of its tasks per node; the first k nodes of it take r tasks each and move to
-                // level g mod q, a remainder of fewer than r tasks goes to one node, which then stays at level g − rem·q.  No level: the step moves nothing and the gang has failed.
-                while ((placed < nt) & !fail & (qc != 0)) {
-                    const int g = KFL_LEVEL_FOR(qc);
-                    fail = g == 0;
-                    int r = kfl_quot(tq, g); r = r > 1 ? r : 1;
-                    const int rem = nt - placed;
-                    int kq = rem; if (r != 1) kq = kfl_div(rem, r);               // whole nodes the rest of the gang fills (0: it is a remainder of fewer than r tasks, on one node)
-                    const int cg = kw::bcast(cnt, (g - 1) & 63);
-                    int k = kq < cg ? kq : cg; k = k > 1 ? k : 1; k = g ? k : 0;  // min(kq, nodes of the level), at least the one node; no level: nothing moves
-                    const int per = r < rem ? r : rem, g2 = g - per * qc;
-                    KFL_EMIT(g, g2, k, per, first + placed);  // (a failed step writes a slot that stays unpublished: whatever its fields hold)
-                    KFL_EVENT(g, g2, k);
-                    placed += k * per;
-                }
-                KFL_T(2);
-                const bool ok = !fail;
-                okm |= (uint64_t)ok << jj;
-                decisions += placed + (int)fail;  // every task placed is a decision (a gang that fits places them all); a gang that found no node for its next task booked that one too
-                rollbacks += 2 * (int)fail;
-                cnt = ok ? cnt : cnt_s; nz = ok ? nz : nz_s; wp = ok ? wp : wp_s;  // Statement.Rollback: nothing was published
-                if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
-                const bool mism = (flag == BF_OK) != ok;  // the job ended differently from its prediction: it is the round's last
-                mismatch |= (int)mism; last_jj = jj; todo = mism ? 0 : todo;
-                KFL_T(3);
             }
             if (mismatch) { n_done = base + last_jj + 1; n_out = last_jj + 1; attempted -= jn - n_out; }
             KFL_T(3);
@@ -223,6 +277,8 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         #undef KFL_ROOM
         #undef KFL_EMIT
         #undef KFL_EVENT
+        #undef KFL_STEP
+        #undef KFL_GANG_END
         if (lane == 0) L.fin = n_done;
         kw::lds_store_rel(&L.head, wp);
         kw::lds_store_rel(&L.done, 1);
@@ -231,7 +287,7 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
             FillStatus s; s.n_done = n_done; s.mismatch = mismatch; s.all_dead = (C > 0 && dead == (C >= 64 ? ~0ull : ((1ull << C) - 1))) ? 1 : 0; s.planned = V; s.floor_stop = 0; s.pad = 0;
             s.decisions = decisions; s.attempted = attempted; s.committed = committed; s.rollbacks = rollbacks; s.ops = ops; s.dead_mask = dead;  // (decisions: the bookkeeper's part is added below)
             s.cycles_total = kw::clock() - tstart; s.cycles_load = a_wait; s.cycles_update = 0; s.cycles_rescan = 0; s.block_loads = 0;  // (cycles_update / cycles_rescan / block_loads / rescans1: the workers' clocks, added below)
-            s.rescans1 = 0; s.rescans2 = wp; s.rescans3 = 0;  // rescans2: commands (a command moves the first k nodes of a level)
+            s.rescans1 = 0; s.rescans2 = wp - n_mark; s.rescans3 = 0;  // rescans2: commands (a command moves the first k nodes of a level; the markers are none)
 #ifdef KFL_PROF
             s.cycles_load = pc[0]; s.cycles_update = pc[1]; s.cycles_rescan = pc[2]; s.block_loads = pc[3]; s.rescans1 = pc[4];  // stretch prologue / decode / the gang / its tail / stretch epilogue
 #endif
@@ -249,10 +305,10 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         int xp = 0, xseen = 0, xc = 0;
         int tail = 0; int64_t w_idle = 0; const int64_t w_start = kw::clock();
         for (;;) {
-            const int head = kw::lds_load_acq(&L.head);
+            const int head = kfl_load(&L.head);
             if (tail == head) {
-                if (kw::lds_load_acq(&L.done) && tail == kw::lds_load_acq(&L.head)) break;
-                const int64_t i0 = kw::clock(); while (kw::lds_load_acq(&L.head) == tail && !kw::lds_load_acq(&L.done)) kw::relax(); w_idle += kw::clock() - i0;
+                if (kfl_load(&L.done) && tail == kfl_load(&L.head)) break;
+                const int64_t i0 = kw::clock(); while (kfl_load(&L.head) == tail && !kfl_load(&L.done)) kw::relax(); w_idle += kw::clock() - i0;
                 continue;
             }
             while (tail < head) {
@@ -290,7 +346,7 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                             left -= m; tb += m * per;
                             if (g2 >= 1) {  // hand the nodes over to the worker of the target level
                                 const int n_w = kw::bcast(xp, g2 - 1);
-                                if (n_w - kw::bcast(xseen, g2 - 1) >= KFL_XR) { int t; while (n_w - (t = kw::lds_load_acq(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == g2 - 1) xseen = t; }
+                                if (n_w - kw::bcast(xseen, g2 - 1) >= KFL_XR) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == g2 - 1) xseen = t; }
                                 const int sl = n_w & (KFL_XR - 1);
                                 if (lane == 0) { L.x[pr][sl].mask = mask; L.x[pr][sl].w = w | (left == 0 ? 1 << 30 : 0); }
                                 kw::lds_store_ordered(&L.x[pr][sl].seq, n_w + 1);
@@ -303,7 +359,7 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                         for (bool last = false; !last;) {
                             const int n_r = kw::bcast(xc, g - 1);
                             const int sl = n_r & (KFL_XR - 1);
-                            if (kw::lds_load_acq(&L.x[pr][sl].seq) != n_r + 1) { const int64_t i0 = kw::clock(); while (kw::lds_load_acq(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; }
+                            if (kfl_load(&L.x[pr][sl].seq) != n_r + 1) { const int64_t i0 = kw::clock(); while (kfl_load(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; }
                             const int wf = kw::bcast(L.x[pr][sl].w, 0), w = wf & 0x3fffffff; const uint64_t mask = kw::bcast(L.x[pr][sl].mask, 0);
                             last = (wf >> 30) & 1;
                             kw::lds_store_ordered(&L.xtail[pr], n_r + 1);
@@ -326,56 +382,55 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         if (lane == 0) { L.w_idle[G - 1] = w_idle; L.w_total[G - 1] = kw::clock() - w_start; }
     } else if (wave == v.LV + 1) {
         // ------------------------------------------------------------------ wavefront LV + 1: the bookkeeper.  It replays the commands on the capacities (lane q − 1: capq) and books,
-        // for every dead-for-good gang, the capacity of its request size at its turn.  A command's job is the walked job whose task range holds the command's tbase.
+        // for every dead-for-good gang, the capacity of its request size at its turn.  A command names its job (bits 23-28); a marker (g = 0) stands in front of every stretch's commands.
         const int qk = lane < C ? (int)c.cls[lane].req[KAI_RES_GPU] : 0x7fffffff;
         const uint32_t tab = kfl_tab(lane, v.LV);
         int capq = 0;
         { const int cnt = lane < v.LV ? L.cnt0[lane] : 0; for (int g = 1; g <= v.LV; g++) capq += kfl_quot(tab, g) * kw::bcast(cnt, g - 1); }
         int dec_v = 0;                     // lane q − 1: Σ of the capacities the dead gangs that ask for q devices met at their turns
-        int base = rp.start, seg_lo = 0;   // the stretch the bookkeeper is in; its jobs below seg_lo are booked
+        int base = rp.start - 64, seg_lo = 0;   // the stretch the bookkeeper is in (none before the first marker); its jobs below seg_lo are booked
+        bool in = false;
         FlStretch s; s.valid = false; s.flag = BF_GATE; s.first = 0; s.nt = 0; s.q = 0; s.is_def = false; s.defm = 0; s.todo = 0;
         uint64_t failm = 0;                // lane q − 1: the stretch's dead-for-good jobs that ask for q devices
+        const uint64_t tab4 = (uint64_t)tab << 4;  // the quotients with g as the index: (tab4 >> 4g) & 15, 0 for g = 0
         auto enter = [&]() {
             const int gi = base + lane; s.valid = gi < V; const int gc = s.valid ? gi : (V > 0 ? V - 1 : 0);
-            s.flag = s.valid ? (int)b.g_flag[gc] : (int)BF_GATE; s.first = s.valid ? b.g_first[gc] : 0; s.nt = s.valid ? b.g_nt[gc] : 0;
+            s.flag = s.valid ? (int)b.g_flag[gc] : (int)BF_GATE; s.nt = s.valid ? b.g_nt[gc] : 0;
             kfl_classify(s, s.valid ? b.g_ucls[gc] : 0, qk, capq);
             failm = 0; if (s.defm) for (int q = 1; q <= v.LV; q++) { const uint64_t m = kw::ballot(s.is_def && s.q == q); if (lane == q - 1) failm = m; }
-            seg_lo = 0;
+            seg_lo = 0; in = true;
         };
         // the dead-for-good jobs [seg_lo, hi) of the stretch book their decisions with the capacities as they are now
         auto book = [&](int hi) { if (hi > seg_lo) { const uint64_t sm = (hi >= 64 ? ~0ull : (1ull << hi) - 1) & ~((1ull << seg_lo) - 1); if (s.defm & sm) dec_v += capq * __builtin_popcountll(failm & sm); seg_lo = hi; } };
-        if (V > rp.start) enter();
         int tail = 0; int64_t w_idle = 0; const int64_t w_start = kw::clock();
         for (;;) {
-            const int head = kw::lds_load_acq(&L.head);
+            const int head = kfl_load(&L.head);
             if (tail == head) {
-                if (kw::lds_load_acq(&L.done) && tail == kw::lds_load_acq(&L.head)) break;
-                const int64_t i0 = kw::clock(); while (kw::lds_load_acq(&L.head) == tail && !kw::lds_load_acq(&L.done)) kw::relax(); w_idle += kw::clock() - i0;
+                if (kfl_load(&L.done) && tail == kfl_load(&L.head)) break;
+                const int64_t i0 = kw::clock(); while (kfl_load(&L.head) == tail && !kfl_load(&L.done)) kw::relax(); w_idle += kw::clock() - i0;
                 continue;
             }
             while (tail < head) {
                 const int nb = head - tail < 64 ? head - tail : 64;
-                const uint64_t mc = L.ring[(tail + lane) & (KFL_RING - 1)];
+                const uint32_t mc = (uint32_t)L.ring[(tail + lane) & (KFL_RING - 1)];
                 for (int ci = 0; ci < nb; ci++) {
-                    const int ca = kw::bcast((int)(uint32_t)mc, ci), tb = kw::bcast((int)(uint32_t)(mc >> 32), ci);
-                    const int g = ca & 15, g2 = (ca >> 4) & 15, k = (ca >> 12) & 0x7ff;
-                    uint64_t hit;
-                    while (!(hit = kw::ballot(((s.todo >> lane) & 1ull) && tb >= s.first && tb < s.first + s.nt)) && base + 64 < V) { book(64); base += 64; enter(); }  // the command's job lies in a later stretch
-                    {   // the dead gangs in front of the command's job met the capacities before it (no branch: an empty segment books nothing)
-                        const int hi = hit ? __builtin_ctzll(hit) : seg_lo;
-                        const uint64_t sm = ((1ull << hi) - 1) & ~((1ull << seg_lo) - 1);
+                    const uint32_t ca = kw::bcast(mc, ci);
+                    const int g = ca & 15, g2 = (ca >> 4) & 15, k = (ca >> 12) & 0x7ff, jj = (ca >> KFL_JOB_SHIFT) & 63;
+                    if (__builtin_expect(g == 0, 0)) { if (in) book(64); base += 64; enter(); continue; }  // a marker: the rest of the stretch behind, the next one classified with the capacities as they are now
+                    {   // the dead gangs in front of the command's job met the capacities before it (no branch: an empty segment books nothing; jj >= seg_lo, the commands come in the jobs' order)
+                        const uint64_t sm = ((1ull << jj) - 1) & ~((1ull << seg_lo) - 1);
                         dec_v += capq * __builtin_popcountll(failm & sm);
-                        seg_lo = hi > seg_lo ? hi : seg_lo;
+                        seg_lo = jj;
                     }
-                    capq -= k * (kfl_quot(tab, g) - kfl_quot(tab, g2));
+                    capq -= k * ((int)((tab4 >> (4 * g)) & 15) - (int)((tab4 >> (4 * g2)) & 15));
                 }
                 tail += nb;
             }
             kw::lds_store_rel(&L.tail[KFL_LMAX], tail);
         }
-        // the stretches behind the last command, up to the last job the counting machine executed
-        const int fin = kw::lds_load_acq(&L.fin);
-        while (base < fin) { const int hi = fin - base < 64 ? fin - base : 64; book(hi); if (base + 64 >= fin) break; base += 64; enter(); }
+        // the last stretch behind its last command, up to the last job the counting machine executed
+        const int fin = kfl_load(&L.fin);
+        if (in) book(fin - base < 64 ? fin - base : 64);
         int total = 0; for (int l = 0; l < v.LV; l++) total += kw::bcast(dec_v, l);
         if (lane == 0) { L.b_dec = total; L.w_idle[KFL_LMAX] = w_idle; L.w_total[KFL_LMAX] = kw::clock() - w_start; }
     }

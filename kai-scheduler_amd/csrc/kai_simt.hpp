@@ -37,6 +37,17 @@ KW_DEV int bcast(int v, int src) { return __builtin_amdgcn_readlane(v, __builtin
 KW_DEV uint32_t bcast(uint32_t v, int src) { return (uint32_t)bcast((int)v, src); }
 KW_DEV uint64_t bcast(uint64_t v, int src) { const int s = __builtin_amdgcn_readfirstlane(src); return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), s) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, s); }
 KW_DEV double bcast(double v, int src) { return __longlong_as_double((long long)bcast((uint64_t)__double_as_longlong(v), src)); }
+// "every lane holds the same value here": v_readfirstlane_b32 puts it into scalar registers, so that what is computed from it (tests, selects, addresses) runs on the scalar unit.
+// Where the compiler already knows that the value is uniform the instruction folds away.  Only in code all lanes of the wavefront run together.
+KW_DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+KW_DEV uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+KW_DEV uint64_t uni(uint64_t v) { return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// `old` with lane `dst`'s value replaced by the uniform `v` (dst the same in all lanes): v_writelane_b32, no compare and no select
+// (clang has no __builtin for it: the declaration binds the name to the compiler's own intrinsic, as the HIP headers do for theirs)
+extern "C" __device__ int kw_llvm_writelane(int v, int dst, int old) __asm("llvm.amdgcn.writelane.i32");
+KW_DEV int writelane(int old, int v, int dst) { return kw_llvm_writelane(__builtin_amdgcn_readfirstlane(v), __builtin_amdgcn_readfirstlane(dst), old); }
+// a hint to the SIMD's arbiter: 0 (default) .. 3, the wavefront with the higher priority issues first (s_setprio)
+template <int P> KW_DEV void set_prio() { __builtin_amdgcn_s_setprio(P); }
 KW_DEV int atomic_add(int32_t* p, int v) { return atomicAdd(p, v); }
 KW_DEV int atomic_min(int32_t* p, int v) { return atomicMin(p, v); }
 KW_DEV int atomic_max(int32_t* p, int v) { return atomicMax(p, v); }
@@ -212,6 +223,9 @@ inline uint64_t wave_max_u64(uint64_t v, int line = __builtin_LINE()) {
     wave_bar(); return m;
 }
 template <class T> inline T bcast(T v, int src, int line = __builtin_LINE()) { return shfl(v, src, line); }
+template <class T> inline T uni(T v) { return v; }  // (the lanes hold the same value by contract; expect_uniform() checks one where a doubt needs settling)
+inline int writelane(int old, int v, int dst) { return lane() == dst ? v : old; }
+template <int P> inline void set_prio() {}
 inline int atomic_add(int32_t* p, int v) { int o = *p; *p = o + v; return o; }
 inline int atomic_min(int32_t* p, int v) { int o = *p; if (v < o) *p = v; return o; }
 inline int atomic_max(int32_t* p, int v) { int o = *p; if (v > o) *p = v; return o; }
