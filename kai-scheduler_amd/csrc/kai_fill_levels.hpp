@@ -8,10 +8,11 @@
 //   * Wavefront 0, the counting machine.  Lane j of a stretch of 64 jobs holds job j.  A gang of one class that the plan predicted dead and that does not fit the capacities at the
 //     stretch's start is dead for good (capacities only shrink during allocate) and takes no part in the walk.  A walked gang is placed OPTIMISTICALLY on the counts — the lowest
 //     non-empty level >= q, whole nodes per step — and its commands are published when its last task has found a level; a gang that runs out of levels is rolled back (counts, mask
-//     and ring position: three registers) having booked the tasks it placed + 1 decisions, exactly what the capacity rule of kai_fill_counts.hpp books.  So this wavefront keeps no
+//     and ring position) having booked the tasks it placed + 1 decisions, exactly what the capacity rule of kai_fill_counts.hpp books.  So this wavefront keeps no
 //     capacities at all.  Outcomes, Statement numbers and operation offsets of a stretch come out of one ballot and one prefix sum at its end.  A command is 8 bytes.
 //     This wavefront's chain of dependent instructions is the kernel's length, so the walk is written for the instruction stream it compiles to: the usual gang
-//     — one class, 1 .. KFL_SHORT tasks — runs through ≈ 100 instructions and two branches, everything but the counts in scalar registers.
+//     — one class, 1 .. KFL_SHORT tasks — runs through ≈ 70 instructions and two branches, everything but the counts in scalar registers, and stores nothing: the commands of a
+//     RUN of such gangs are held in lanes and written to the ring by all lanes at once when the run ends.
 //   * Wavefronts 1 .. L, the set workers: level g belongs to wavefront g, alone.  Its words, its two summaries and its first node are that wavefront's uniform state (the word that
 //     holds the first node is cached in registers: removing the level's first node — what every command does — reads nothing from LDS while that word lasts).  A worker looks at 64
 //     commands at a time, one per lane, and walks the ones that name its level: as the SOURCE it removes the level's first k nodes, writes the tasks' nodes and hands (word, mask) to
@@ -33,7 +34,7 @@ namespace kai {
 constexpr int KFL_LMAX = 8;                                // levels = worker wavefronts
 constexpr int KFL_RING = 4096;                             // commands the ring holds (a gang, <= KB_PLACED_MAX commands, is written in full before it is published)
 constexpr int KFL_XR = 32;                                 // entries of a hand-over ring
-constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": the stretch reserves its commands' room in the ring up front
+constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": it is walked in a run (its first two commands held in lanes; a third step sends it the long way)
 constexpr int KFL_JOB_SHIFT = 23;                          // a command's bits 23-28: its job's index within the stretch (or-ed in by the counting machine: kfl_cmd knows nothing of it)
 constexpr int KFL_PAIRS = KFL_LMAX * (KFL_LMAX - 1) / 2;   // (source level g, target level g2 < g)
 // a command, 8 bytes: bits 0-3 g, 4-7 g2, 8-11 per, 12-22 k | the upper word: tbase — the first k nodes of level g take `per` tasks each and move to level g2 (0: no level); their tasks are t_node[tbase ..)
@@ -43,7 +44,8 @@ struct FlMove { uint64_t mask; int32_t w; int32_t seq; };  // the nodes `mask` o
 struct FlLds {
     uint64_t ring[KFL_RING];
     uint64_t dummy[64];            // where the lanes other than lane 0 put their copy of a command (a store without a branch)
-    FlMove x[KFL_PAIRS][KFL_XR];
+    FlMove x[KFL_PAIRS + 1][KFL_XR];  // (the last one: where a hand-over to no level goes — a store without a branch, nobody reads it)
+    FlMove xdummy[64];             // ... and where the lanes other than lane 0 put their copy of a hand-over entry
     int32_t xtail[KFL_PAIRS];      // entries the pair's consumer has taken
     int32_t cnt0[KBK_GMAX];
     int32_t tail[KFL_LMAX + 1];    // commands worker g (index g − 1) / the bookkeeper (index KFL_LMAX) has passed
@@ -58,7 +60,7 @@ KW_BODY int kfl_div(int a, int b) {
 }
 // uniform accesses of a worker to its own level's LDS words: every lane reads the same address and takes lane 0's value (a scalar from then on); lane 0 writes
 KW_BODY uint64_t kfl_read(KW_LDS_PTR(uint64_t) p) { return kw::bcast(*p, 0); }
-KW_BODY void kfl_write(KW_LDS_PTR(uint64_t) p, uint64_t v) { if (kw::lane() == 0) *p = v; }
+KW_BODY void kfl_write(KW_LDS_PTR(uint64_t) p, uint64_t v, KW_LDS_PTR(uint64_t) dummy) { KW_LDS_PTR(uint64_t) q = kw::lane() == 0 ? p : dummy + kw::lane(); *q = v; }  // (the other lanes into a slot of their own: one store, no branch)
 // a counter another wavefront publishes (acquire), as a scalar: every lane reads the same address
 KW_BODY int kfl_load(const int32_t* p) { return kw::uni(kw::lds_load_acq(p)); }
 // one stretch of 64 planned jobs as the counting machine and the bookkeeper both see it: lane j holds job j
@@ -90,7 +92,7 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     if (tid < KBK_GMAX) L.cnt0[tid] = 0;
     if (tid <= KFL_LMAX) { L.tail[tid] = 0; L.w_idle[tid] = 0; L.w_total[tid] = 0; }
     if (tid < KFL_PAIRS) L.xtail[tid] = 0;
-    for (int i = tid; i < KFL_PAIRS * KFL_XR; i += T) L.x[i / KFL_XR][i % KFL_XR].seq = 0;
+    for (int i = tid; i < (KFL_PAIRS + 1) * KFL_XR; i += T) L.x[i / KFL_XR][i % KFL_XR].seq = 0;
     if (tid == 0) { L.head = 0; L.done = 0; L.fin = 0; L.b_dec = 0; }
     for (int i = tid; i < v.LV * v.NW; i += T) v.gw[i] = b.bk_words[i];
     kw::sync();
@@ -146,23 +148,30 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         // one step of a gang of ONE class, whole nodes: the lowest non-empty level g >= q holds r = g / q of its tasks per node; the first k nodes of it take r tasks each and move to
         // level g mod q, a remainder of fewer than r tasks goes to one node, which then stays at level g − rem·q.  No level: the step moves nothing and the gang has failed (it writes
         // a slot that stays unpublished: whatever its fields hold).
-        #define KFL_STEP() do { \
-            const int g = KFL_LEVEL_FOR(qc), gm1 = g - 1; \
-            fail = (int)((uint32_t)gm1 >> 31);  /* g == 0 */ \
-            int r = (int)((tq >> ((4 * g - 4) & 31)) & 15u); r = r > 1 ? r : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
-            const int rem = nt - placed; \
-            const int kq = (int)(((uint32_t)rem * (uint32_t)kw::bcast(invq, r - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
-            const int cg = kw::bcast(cnt, gm1 & 63); \
-            int k = kq < cg ? kq : cg; k = k > 1 ? k : 1; k &= fail - 1;  /* min(kq, nodes of the level), at least the one node; no level: nothing moves */ \
-            const int per = r < rem ? r : rem, g2 = g - per * qc; \
-            KFL_EMIT(g, g2, k, per, first + placed); \
-            KFL_EVENT(g, g2, k, cg); \
-            placed += k * per; } while (0)
-        // a gang's end: its outcome bit, what it booked (every task placed is a decision — a gang that fits places them all —, a gang that found no node for its next task booked that
-        // one too), Statement.Rollback (nothing was published: the counts, the mask and the ring position, the counts being the one vector select), and whether it ended as predicted
+        #define KFL_STEP(S, EMIT) \
+            const uint32_t lv##S = nz >> (qc - 1); \
+            ok = kw::nonzero01(lv##S);  /* a level >= q holds a node — as a number, not as a comparison (kai_simt.hpp) */ \
+            const int g##S = lv##S ? qc + __builtin_ctz(lv##S) : 0, gm1##S = g##S - 1; \
+            int r##S = (int)((tq >> ((4 * g##S - 4) & 31)) & 15u); r##S = r##S > 1 ? r##S : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
+            const int rem##S = nt - placed; \
+            const int kq##S = (int)(((uint32_t)rem##S * (uint32_t)kw::bcast(invq, r##S - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
+            const int cg##S = kw::bcast(cnt, gm1##S & 63); \
+            int k##S = kq##S < cg##S ? kq##S : cg##S; k##S = (k##S > 1 ? k##S : 1) * ok;  /* min(kq, nodes of the level), at least the one node; no level: nothing moves */ \
+            const int per##S = r##S < rem##S ? r##S : rem##S, g2##S = g##S - per##S * qc; \
+            EMIT(g##S, g2##S, k##S, per##S); \
+            KFL_EVENT(g##S, g2##S, k##S, cg##S); \
+            placed += k##S * per##S
+        #define KFL_EMIT_RING(g_, g2_, k_, per_) KFL_EMIT(g_, g2_, k_, per_, first + placed)
+        // a command's lower word without its job's index, held in lane jj of a register until the run is flushed (a gang that fails holds whatever: it is never stored)
+        #define KFL_LOW(g_, g2_, k_, per_) (int)((uint32_t)(g_) | ((uint32_t)(g2_) << 4) | ((uint32_t)(per_) << 8) | ((uint32_t)(k_) << 12))
+        #define KFL_HOLD0(g_, g2_, k_, per_) c0 = kw::writelane(c0, KFL_LOW(g_, g2_, k_, per_), jj)
+        #define KFL_HOLD1(g_, g2_, k_, per_) c1 = kw::writelane(c1, KFL_LOW(g_, g2_, k_, per_), jj)
+        // the end of a gang that went the long way: its outcome bit, what it placed before it failed (a stretch's decisions and rollbacks are summed up at its end: every task of a
+        // committed gang is a decision, a gang that found no node for its next task booked the ones it placed and that one), Statement.Rollback (nothing was published: the counts, the
+        // mask and the ring position), and whether it ended as predicted
         #define KFL_GANG_END() \
-            okm |= (uint64_t)(uint32_t)(1 - fail) << jj; \
-            decisions += placed + fail; rollbacks += 2 * fail; \
+            okm |= (uint64_t)(uint32_t)(1 - fail) << jj; failm |= (uint64_t)(uint32_t)fail << jj; \
+            extra += placed & (0 - fail); \
             cnt = fail ? cnt_s : cnt; nz = fail ? nz_s : nz; wp = fail ? wp_s : wp; \
             const int mism = (int)((uint32_t)(flag - 1) >> 31) ^ fail ^ 1;  /* (flag == BF_OK) != ok — the job ended differently from its prediction: it is the round's last */ \
             mismatch |= mism; last_jj = jj
@@ -179,15 +188,15 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
             int capq = 0;  // lane q − 1: the tasks that ask for q devices the levels hold at the stretch's start
             for (int g = 1; g <= v.LV; g++) capq += kfl_quot(tab, g) * kw::bcast(cnt, g - 1);
             kfl_classify(s, my_ucls, qk, capq);
-            // a job's parameters in one word: flag (2 bits), devices (5 bits), tasks (up to KB_PLACED_MAX: 11 bits), bit 18: the long way (several classes, more tasks than the
+            // a job's parameters in one word: flag (2 bits), devices (5 bits), tasks (up to KB_PLACED_MAX: 11 bits), bit 19: predicted to fit, bit 18: the long way (several classes, more tasks than the
             // stretch's reservation in the ring covers, or none at all: the short way takes its first step without asking)
-            const int my_pack = s.flag | (s.q << 2) | (s.nt << 7) | ((s.q == 0 || s.nt > KFL_SHORT || s.nt < 1) ? 1 << 18 : 0);
+            const int my_pack = s.flag | (s.q << 2) | (s.nt << 7) | ((s.q == 0 || s.nt > KFL_SHORT || s.nt < 1) ? 1 << 18 : 0) | (s.flag == BF_OK ? 1 << 19 : 0);
             const uint32_t my_tq = kw::shfl(tab, s.q >= 1 ? s.q - 1 : 63);  // the quotients g / q of the job's request
-            const uint64_t longm = kw::ballot((my_pack >> 18) != 0);
-            uint64_t todo = s.todo, okm = 0;  // okm: jobs of this stretch that committed
-            int n_out = jn, last_jj = 0;
+            uint64_t longm = kw::ballot(((my_pack >> 18) & 1) != 0);
+            uint64_t todo = s.todo, okm = 0, failm = 0, okw = 0;  // okm / failm: jobs of this stretch that committed / that were walked and found no room; okw: the walked jobs of its runs that found room
+            int n_out = jn, last_jj = 0, extra = 0;  // extra: tasks the failed gangs had placed before they failed
             attempted += jn; n_done = base + jn;
-            KFL_ROOM(64 * KFL_SHORT + 1);  // room for the stretch's marker and every short gang of it: no check per gang
+            KFL_ROOM(1);  // room for the stretch's marker (a run asks for the room of its commands when it is flushed, a long gang before it starts: no check per gang)
 #if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(my_tq), "v"(my_pack) : "memory");  // the stretch's shuffles have landed: the walk below never waits on the LDS counter (its own command stores stay in flight)
 #endif
@@ -196,35 +205,64 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
             KFL_T(0);
             // (a conditional branch costs this wavefront 22 - 31 cycles whether it is taken or not, a scalar instruction 5 - 6, a dependent vector instruction 7, a vector compare that
             // feeds the scalar unit 30 — tools/micro/issue_rate.hip.  So the usual gang — one class, 1 .. KFL_SHORT tasks — runs straight through: the short gangs in front of the next
-            // long one are walked by a loop that holds nothing else, its first step without a test, one rarely taken branch for further steps, and ONE test at its end for "more to
-            // walk, nothing to publish, predicted right".  Everything but the counts lives in scalar registers.)
+            // long one, a RUN, are walked by a loop that holds nothing else, its first step without a test, one rarely taken branch for a second step, and ONE test at its end for
+            // "more to walk, predicted right".  Everything but the counts lives in scalar registers.
+            // A run stores nothing: the lower word of a gang's command goes into lane jj of c0, that of a second step into c1, and the run is FLUSHED at its end — every lane forms
+            // the upper words and the job bits of its own gang's commands, a prefix sum gives it their place in the ring, head is published once.  The ring receives the words in
+            // the jobs' order, as if every gang had written its own.  A first step that finds no level moves nothing (k = 0), so only a gang that takes a second step needs the
+            // state in front of it: rebuilt there from the first step's values.  A short gang that needs a third step leaves the run and goes the long way from the start.)
             while (todo) {
                 const uint64_t lm = todo & longm;
                 const uint64_t below = lm ? (lm & (0 - lm)) - 1 : ~0ull;  // the jobs in front of the next long one
                 uint64_t hot = todo & below;
                 todo &= ~below;
                 if (hot) {
-                    uint64_t go;
+                    const uint64_t run0 = hot; uint64_t twor = 0, rest = 0;  // the run's jobs / the ones among them that committed with two commands / the ones a third step left unwalked
+                    int c0 = 0, c1 = 0, jj, pred, ok;
                     do {
-                        const int jj = __builtin_ctzll(hot); hot &= hot - 1;
-                        const int pack = kw::bcast(my_pack, jj), first = kw::bcast(s.first, jj);
+                        jj = __builtin_ctzll(hot); hot &= hot - 1;
+                        const int pack = kw::bcast(my_pack, jj);
                         const uint32_t tq = kw::bcast(my_tq, jj);
-                        const int flag = pack & 3, qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
-                        const uint64_t jbits = (uint64_t)((uint32_t)jj << KFL_JOB_SHIFT);
+                        const int qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
+                        pred = (pack >> 19) & 1;  // flag == BF_OK
                         KFL_T(1);
-                        // the gang on the counts; its commands stay unpublished until its last task has found a level
-                        const int cnt_s = cnt, wp_s = wp; const uint32_t nz_s = nz;
-                        int placed = 0, fail;
-                        KFL_STEP();
-                        while (__builtin_expect((int)((placed < nt) & (fail == 0)), 0)) KFL_STEP();
+                        const uint32_t nz_s = nz;
+                        int placed = 0;
+                        KFL_STEP(A, KFL_HOLD0);
+                        if (__builtin_expect(placed < nt * ok, 0)) {
+                            // the counts in front of the gang: the first step taken back
+                            int cnt_s = kw::writelane(cnt, kw::bcast(cnt, (g2A - 1) & 63) - kA, (g2A - 1) & 63); cnt_s = kw::writelane(cnt_s, cgA, gm1A & 63);
+                            KFL_STEP(B, KFL_HOLD1);
+                            if (!ok) { cnt = cnt_s; nz = nz_s; extra += placed; }  // Statement.Rollback: it booked the tasks it placed and the one that found no node
+                            else if (placed < nt) {  // a third step: not in lanes — the run ends in front of this gang, which then goes the long way (no outcome here: `ok` is set to what was predicted and taken out of okw below)
+                                cnt = cnt_s; nz = nz_s; longm |= 1ull << jj; rest = hot | (1ull << jj); hot = 0; ok = pred;
+                            } else twor |= 1ull << jj;
+                        }
                         KFL_T(2);
-                        KFL_GANG_END();
-                        go = hot & (uint64_t)((int64_t)(int32_t)kw::uni((int)(((uint32_t)mism | ((uint32_t)(wp - pub) >> 6)) - 1u)) >> 63);  // (wp >= pub: the difference reaches 64 when bit 6 or a higher one is set)
+                        okw |= (uint64_t)(uint32_t)ok << jj;
+                        hot = kw::opaque(pred == ok ? hot : (uint64_t)0);  // a job that ends differently from its prediction is the round's last: nothing behind it is walked
                         KFL_T(3);
-                    } while (go);
+                    } while (hot);
+                    mismatch |= pred ^ ok;
+                    const uint64_t walked = run0 & ((2ull << jj) - 1) & ~rest, okr = walked & okw;  // (the jobs of the run up to the last one walked)
+                    failm |= walked & ~okw; hot |= rest;
+                    // the flush: lane j stores the commands of job j
+                    okm |= okr;
+                    if (mismatch) last_jj = 63 - __builtin_clzll(walked);
+                    if (okr) {
+                        const int n_my = (int)((okr >> lane) & 1ull) + (int)((twor >> lane) & 1ull);
+                        const int incl = kw::wave_scan_add(n_my), n_run = kw::bcast(incl, 63);
+                        KFL_ROOM(n_run);
+                        const int pos = wp + incl - n_my;
+                        const uint32_t jb = (uint32_t)lane << KFL_JOB_SHIFT;
+                        if (n_my >= 1) L.ring[pos & (KFL_RING - 1)] = (uint64_t)((uint32_t)c0 | jb) | ((uint64_t)(uint32_t)s.first << 32);
+                        if (n_my >= 2) L.ring[(pos + 1) & (KFL_RING - 1)] = (uint64_t)((uint32_t)c1 | jb) | ((uint64_t)(uint32_t)(s.first + ((c0 >> 12) & 0x7ff) * ((c0 >> 8) & 15)) << 32);
+                        wp += n_run;
+                        kw::lds_store_rel(&L.head, wp); pub = wp;
+                    }
+                    KFL_T(3);
                 }
                 todo |= hot;
-                if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
                 if (mismatch) break;
                 if (!hot && lm) {
                     // the long way: a gang of several classes task by task, a gang of one class with more tasks than the stretch reserved room for (or none)
@@ -235,22 +273,23 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                     const uint64_t jbits = (uint64_t)((uint32_t)jj << KFL_JOB_SHIFT);
                     KFL_T(1);
                     const int cnt_s = cnt, wp_s = wp; const uint32_t nz_s = nz;
-                    int placed = 0, fail = 0;
-                    KFL_ROOM(nt + 64 * KFL_SHORT);
+                    int placed = 0, ok = 1;
+                    KFL_ROOM(nt);
                     if (!qc) {
-                        for (int tb = 0; tb < nt && !fail; tb += 64) {
+                        for (int tb = 0; tb < nt && ok; tb += 64) {
                             const int my_cls = tb + lane < nt ? b.t_cls[first + tb + lane] : 0;
                             const int tc = nt - tb < 64 ? nt - tb : 64;
                             for (int ti = 0; ti < tc; ti++) {
                                 const int q1 = kw::bcast(qk, kw::bcast(my_cls, ti));
                                 const int g = q1 <= 31 ? KFL_LEVEL_FOR(q1) : 0;
-                                if (!g) { fail = 1; break; }
+                                if (!g) { ok = 0; break; }
                                 KFL_EMIT(g, g - q1, 1, 1, first + placed);
                                 KFL_EVENT(g, g - q1, 1, kw::bcast(cnt, g - 1));
                                 placed++;
                             }
                         }
-                    } else while ((placed < nt) & (fail == 0)) KFL_STEP();
+                    } else while ((placed < nt) & (ok != 0)) { KFL_STEP(L, KFL_EMIT_RING); }
+                    const int fail = ok ^ 1;
                     KFL_T(2);
                     KFL_GANG_END();
                     if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
@@ -262,13 +301,13 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
             KFL_T(3);
             {   // the stretch's outcomes: what every job ended with, its Statement number and the offset of its operations among the round's (a ballot and a prefix sum)
                 const uint64_t outm = n_out >= 64 ? ~0ull : (1ull << n_out) - 1;
-                const int ndef = __builtin_popcountll(s.defm & outm);  // (the capacities at their turns: the bookkeeper's part)
-                decisions += ndef; rollbacks += 2 * ndef;
+                const int nfail = __builtin_popcountll(s.defm & outm) + __builtin_popcountll(failm);  // dead for good (the capacities at their turns: the bookkeeper's part) or walked without room
+                decisions += nfail + extra; rollbacks += 2 * nfail;
                 const bool my_ok = (okm >> lane) & 1ull;
                 const int myv = my_ok ? s.nt : 0, incl = kw::wave_scan_add(myv);
                 const int my_stmt = committed + rp.stmt0 + __builtin_popcountll(okm & ((1ull << lane) - 1)), my_opoff = ops + rp.ops0 + incl - myv;
                 if (lane < n_out) { b.g_out[base + lane] = (uint8_t)(my_ok ? BF_OK : BF_DEAD); b.g_opoff[base + lane] = my_opoff; b.g_stmt[base + lane] = my_stmt; }
-                committed += __builtin_popcountll(okm); ops += kw::bcast(incl, 63);
+                committed += __builtin_popcountll(okm); ops += kw::bcast(incl, 63); decisions += kw::bcast(incl, 63);  // every task of a committed gang was a decision
             }
             if (wp != pub) { kw::lds_store_rel(&L.head, wp); pub = wp; }
             KFL_T(4);
@@ -278,6 +317,10 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         #undef KFL_EMIT
         #undef KFL_EVENT
         #undef KFL_STEP
+        #undef KFL_EMIT_RING
+        #undef KFL_LOW
+        #undef KFL_HOLD0
+        #undef KFL_HOLD1
         #undef KFL_GANG_END
         if (lane == 0) L.fin = n_done;
         kw::lds_store_rel(&L.head, wp);
@@ -296,6 +339,7 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     } else if (wave <= v.LV) {
         // ------------------------------------------------------------------ wavefront G = 1 .. LV: the worker of level G.  Everything here is uniform over the wavefront.
         const int G = wave, lw = (G - 1) * v.NW, l1 = (G - 1) * v.NW1;
+        KW_LDS_PTR(uint64_t) dm = (KW_LDS_PTR(uint64_t))&L.dummy[0];
         uint64_t s2 = kw::ballot(lane < v.NW1 && v.s1[l1 + (lane < v.NW1 ? lane : 0)] != 0);  // second summary: bit j = the 64 words of group j hold a node
         int firstn = KB_INF, cw = -1; uint64_t curw = 0;  // the level's first node (lowest name rank), the word that holds it (index and current value)
         auto first_of_group = [&](int w1, uint64_t m1) { cw = w1 * 64 + __builtin_ctzll(m1); curw = kfl_read(&v.gw[lw + cw]); firstn = (cw << 6) + __builtin_ctzll(curw); };
@@ -323,7 +367,27 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                     if (g == G) {
                         // SOURCE: the level's first k nodes leave it, `per` tasks on each
                         const int per = (ca >> 8) & 15; int left = (ca >> 12) & 0x7ff, tb = kw::bcast((int)(uint32_t)(mc >> 32), ci);
-                        const int pr = g2 >= 1 ? kfl_pair(G, g2) : 0;
+                        const int pr = g2 >= 1 ? kfl_pair(G, g2) : KFL_PAIRS;  // (no level: the ring nobody reads)
+                        if (__builtin_expect(left == 1, 1)) {
+                            // the usual command, straight through: ONE node, the level's first, leaves with `per` tasks on it; the word it sat in stays non-empty and the hand-over ring has
+                            // room (either of the two failing: one rarely taken exit each).  Every LDS store goes through a pointer that is lane 0's target or the lane's own dummy slot.
+                            const int w = cw; const uint64_t mask = curw & (0 - curw), neww = curw ^ mask;
+                            b.t_node[tb + (lane < per ? lane : per - 1)] = firstn;  // (its tasks all sit on it, per <= 8; the lanes beyond them store the last one's again: no branch)
+                            kfl_write(&v.gw[lw + w], neww, dm);
+                            const int xl = (g2 - 1) & 63, n_w = kw::bcast(xp, xl);  // (no level: lane 63, which is never counted up)
+                            if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
+                            KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
+                            e->mask = mask; e->w = w | (1 << 30);
+                            kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
+                            xp += lane == g2 - 1 ? 1 : 0;
+                            if (__builtin_expect(neww != 0, 1)) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
+                            else {  // the word is empty: its bit in the first summary goes, and the level's first node is the first node of the next word
+                                const int w1 = w >> 6; const uint64_t m1 = kfl_read(&v.s1[l1 + w1]) & ~(1ull << (w & 63));
+                                kfl_write(&v.s1[l1 + w1], m1, dm);
+                                if (m1) first_of_group(w1, m1); else { s2 &= ~(1ull << w1); refill(); }
+                            }
+                            left = 0;
+                        }
                         while (left > 0) {
                             const int w = cw; const uint64_t word = curw;
                             int m = 1; uint64_t mask = word & (0 - word);
@@ -336,11 +400,11 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                                 }
                             } else if (lane < per) b.t_node[tb + lane] = firstn;  // one node (the usual command): its tasks all sit on it (per <= 8)
                             const uint64_t neww = word ^ mask;
-                            kfl_write(&v.gw[lw + w], neww);
+                            kfl_write(&v.gw[lw + w], neww, dm);
                             if (neww) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
                             else {  // the word is empty: its bit in the first summary goes, and the level's first node is the first node of the next word
                                 const int w1 = w >> 6; const uint64_t m1 = kfl_read(&v.s1[l1 + w1]) & ~(1ull << (w & 63));
-                                kfl_write(&v.s1[l1 + w1], m1);
+                                kfl_write(&v.s1[l1 + w1], m1, dm);
                                 if (m1) first_of_group(w1, m1); else { s2 &= ~(1ull << w1); refill(); }
                             }
                             left -= m; tb += m * per;
@@ -359,18 +423,22 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                         for (bool last = false; !last;) {
                             const int n_r = kw::bcast(xc, g - 1);
                             const int sl = n_r & (KFL_XR - 1);
-                            if (kfl_load(&L.x[pr][sl].seq) != n_r + 1) { const int64_t i0 = kw::clock(); while (kfl_load(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; }
-                            const int wf = kw::bcast(L.x[pr][sl].w, 0), w = wf & 0x3fffffff; const uint64_t mask = kw::bcast(L.x[pr][sl].mask, 0);
+                            // the sequence number, then the entry behind it, in one trip to the LDS: the LDS serves a wavefront's reads in issue order and the producer stored the number last
+                            // (the reads of the entry are atomic ones so that the compiler leaves them in front of the test)
+                            int sq = kw::lds_load_ordered(&L.x[pr][sl].seq), wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); uint64_t mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask);
+                            if (__builtin_expect(kw::uni(sq) != n_r + 1, 0)) { const int64_t i0 = kw::clock(); while (kfl_load(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask); }
+                            const int wf = kw::bcast(wf_v, 0), w = wf & 0x3fffffff; const uint64_t mask = kw::bcast(mk_v, 0);
                             last = (wf >> 30) & 1;
                             kw::lds_store_ordered(&L.xtail[pr], n_r + 1);
                             if (lane == g - 1) xc++;
-                            if (w == cw) { curw |= mask; kfl_write(&v.gw[lw + w], curw); firstn = (w << 6) + __builtin_ctzll(curw); }
+                            if (w == cw) { curw |= mask; kfl_write(&v.gw[lw + w], curw, dm); firstn = (w << 6) + __builtin_ctzll(curw); }
                             else {
                                 const uint64_t old = kfl_read(&v.gw[lw + w]), nw = old | mask;
-                                kfl_write(&v.gw[lw + w], nw);
-                                if (!old) { const int w1 = w >> 6; const uint64_t o1 = kfl_read(&v.s1[l1 + w1]); kfl_write(&v.s1[l1 + w1], o1 | (1ull << (w & 63))); if (!o1) s2 |= 1ull << w1; }
-                                const int n = (w << 6) + __builtin_ctzll(mask);
-                                if (n < firstn) { firstn = n; cw = w; curw = nw; }  // (every node the word held before lies at or above the old first node)
+                                kfl_write(&v.gw[lw + w], nw, dm);
+                                if (!old) { const int w1 = w >> 6; const uint64_t o1 = kfl_read(&v.s1[l1 + w1]); kfl_write(&v.s1[l1 + w1], o1 | (1ull << (w & 63)), dm); if (!o1) s2 |= 1ull << w1; }
+                                const int n = (w << 6) + __builtin_ctzll(mask), fn = kw::uni(firstn);
+                                const bool lower = n < fn;  // (every node the word held before lies at or above the old first node)
+                                firstn = lower ? n : fn; cw = lower ? w : cw; curw = lower ? nw : curw;
                             }
                         }
                     }

@@ -46,6 +46,11 @@ KW_DEV uint64_t uni(uint64_t v) { return ((uint64_t)(uint32_t)__builtin_amdgcn_r
 // (clang has no __builtin for it: the declaration binds the name to the compiler's own intrinsic, as the HIP headers do for theirs)
 extern "C" __device__ int kw_llvm_writelane(int v, int dst, int old) __asm("llvm.amdgcn.writelane.i32");
 KW_DEV int writelane(int old, int v, int dst) { return kw_llvm_writelane(__builtin_amdgcn_readfirstlane(v), __builtin_amdgcn_readfirstlane(dst), old); }
+// v != 0 as the number 0 / 1 for a uniform v (the same in every lane), in ONE scalar instruction the compiler knows nothing about: a truth value that is selected on, multiplied with and
+// added up comes back from the compiler as a lane mask, a vector select and a read back into a scalar register (30 cycles on a chain of dependent instructions)
+KW_DEV int nonzero01(uint32_t v) { int r; asm("s_min_u32 %0, %1, 1" : "=s"(r) : "s"(v) : "scc"); return r; }
+// a uniform 64-bit value the compiler knows nothing about from here on
+KW_DEV uint64_t opaque(uint64_t v) { v = uni(v); asm("" : "+s"(v)); return v; }
 // a hint to the SIMD's arbiter: 0 (default) .. 3, the wavefront with the higher priority issues first (s_setprio)
 template <int P> KW_DEV void set_prio() { __builtin_amdgcn_s_setprio(P); }
 KW_DEV int atomic_add(int32_t* p, int v) { return atomicAdd(p, v); }
@@ -75,6 +80,11 @@ KW_DEV void relax() { __builtin_amdgcn_s_sleep(1); }
 // ... the same hand-over without waiting for the producer's own stores to land: the LDS executes one wavefront's instructions in issue order, so a payload stored before the counter is
 // in place before it; all the producer must do is keep the compiler from reordering the two stores (kai_fill_levels.hpp: a worker's hand-over entries)
 KW_DEV void lds_store_ordered(int32_t* p, int v) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// ... and the consumer's side of it: the counter read now, what is read after it served behind it by the LDS — no wait between the two reads, which come back in one trip.  The caller tests the
+// counter and uses the payload only if it is the one it waits for
+KW_DEV int lds_load_ordered(const int32_t* p) { const int v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); return v; }
+KW_DEV int lds_load_relaxed(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+KW_DEV uint64_t lds_load_relaxed(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 }  // namespace kw
 
 #else  // ---------------------------------------------------------------------------------------------- host emulator (tests only)
@@ -225,6 +235,8 @@ inline uint64_t wave_max_u64(uint64_t v, int line = __builtin_LINE()) {
 template <class T> inline T bcast(T v, int src, int line = __builtin_LINE()) { return shfl(v, src, line); }
 template <class T> inline T uni(T v) { return v; }  // (the lanes hold the same value by contract; expect_uniform() checks one where a doubt needs settling)
 inline int writelane(int old, int v, int dst) { return lane() == dst ? v : old; }
+inline int nonzero01(uint32_t v) { return v ? 1 : 0; }
+inline uint64_t opaque(uint64_t v) { return v; }
 template <int P> inline void set_prio() {}
 inline int atomic_add(int32_t* p, int v) { int o = *p; *p = o + v; return o; }
 inline int atomic_min(int32_t* p, int v) { int o = *p; if (v < o) *p = v; return o; }
@@ -240,6 +252,9 @@ inline void fence_wg() {}
 inline int lds_load_acq(const int32_t* p) { return *p; }
 inline void lds_store_rel(int32_t* p, int v) { *p = v; }
 inline void lds_store_ordered(int32_t* p, int v) { *p = v; }
+inline int lds_load_ordered(const int32_t* p) { return *p; }
+inline int lds_load_relaxed(const int32_t* p) { return *p; }
+inline uint64_t lds_load_relaxed(const uint64_t* p) { return *p; }
 inline void relax(int line = __builtin_LINE()) { wave_bar(line); }  // the whole wave parks: the scheduler lets the other wavefronts of the workgroup run
 inline void wave_sync(int line = __builtin_LINE()) { wave_bar(line); }
 inline void lds_order(int line = __builtin_LINE()) { wave_bar(line); }
