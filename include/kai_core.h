@@ -147,7 +147,11 @@ typedef struct kai_config {
     int64_t min_node_gpu_memory;          /* ClusterInfo.MinNodeGPUMemory */
     int32_t queue_depth[4];               /* per kai_action; -1 = infinite (framework/session.go:398-404) */
     int32_t engine_mode;                  /* 0 = default (allocate: batch plan/fill/apply path when the action qualifies, else the sequential engine);
-                                             1 = force brute-force node scans; 2 = class index without the staged job path; 3 = sequential engine only (debug / A-B) */
+                                             1 = force brute-force node scans; 2 = class index without the staged job path; 3 = sequential engine only (debug / A-B).
+                                             The batch path's fill runs on sets of nodes by free devices when every scan class is placed on the GPU and asks for a whole number
+                                             of 1 .. 16 devices and no other resource of a node can bind before its devices do — under gpu_strategy = KAI_BINPACK, and under
+                                             KAI_SPREAD when, besides, every node with a free device carries ONE device count (nvidia.com/gpu.count, else allocatable) and no
+                                             class needs a node bitmap of its own; every other session runs the general fill kernel.  Same results either way. */
     int32_t reserved[7];
     /* minruntime plugin (plugins/minruntime/minruntime.go:40-100): "now" of the cycle, plugin-argument defaults, reclaim resolve method */
     int64_t now_ns;

@@ -84,6 +84,8 @@ inline size_t batch_fill_lds(const KaiCtx& c, int& l1_in_lds) {
 // The bucket fill (kai_fill_buckets.hpp) takes the action when k_bucket_build's proof holds for every node and the sets fit the LDS of one CU.
 inline bool batch_bucket_params(const KaiCtx& c, const BucketMeta& m, BucketParams& bp, size_t& dyn) {
     bp = BucketParams{}; dyn = 0;
+    // spread classes: one divisor of the score on every node that can take a task (k_bucket_build's minimum and maximum agree; no such node: nothing to agree on)
+    if (c.gpu_strategy == KAI_SPREAD && (m.div_max != 0 || m.div_nmin != 0) && m.div_max != KBK_DIV_MAX + 1 - m.div_nmin) return false;
     if (m.bad || c.C < 1 || c.C > 64 || !(c.plugins & KAI_PLUGIN_NODEPLACEMENT)) return false;
     bp.levels = std::max(1, (int)m.max_free); bp.nw = c.NB; bp.nw1 = (c.NB + 63) / 64; bp.n_ok = 0;
     if (bp.levels > KBK_GMAX || bp.nw1 > 64) return false;
@@ -162,7 +164,7 @@ int batch_allocate(L& l, KaiCtx& c, const HostPrep::BatchShape& shape, BatchStat
     int l1_in_lds = 0; const size_t dyn = batch_fill_lds(c, l1_in_lds);
     RoundParams rp{}; rp.mode = 1;
     FillStatus fs{};
-    // bin-packed GPU classes on nodes where only the devices can bind: the fill over sets of nodes by free devices, all in LDS (kai_fill_buckets.hpp);
+    // bin-packed or spread GPU classes on nodes where only the devices can bind: the fill over sets of nodes by free devices, all in LDS (kai_fill_buckets.hpp);
     // KAI_FILL_GENERAL=1 keeps the general kernel (A/B runs, tests)
     bool buckets = false; BucketParams bp{}; size_t dyn_bk = 0;
     if (try_sets) {
@@ -178,6 +180,9 @@ int batch_allocate(L& l, KaiCtx& c, const HostPrep::BatchShape& shape, BatchStat
     // ... and, up to eight levels, with a wavefront per level behind the counting machine (kai_fill_levels.hpp); KAI_FILL_TWO_WORKERS=1 keeps the kernel of kai_fill_counts.hpp (A/B runs, tests)
     const bool levels = counts && bp.levels <= KFL_LMAX && !std::getenv("KAI_FILL_TWO_WORKERS") && dyn_bk + sizeof(FlLds) <= (size_t)(160 - 16) * 1024;
     const int fill_tb = levels ? 64 * (bp.levels + 2) : 256;  // the counting machine, a worker per level, the bookkeeper
+    // spread classes take the sets on the counting machines only (k_fill_buckets is bin-pack): a class with a static bitmap, the one-wave and unbatched switches or sets beyond the
+    // LDS budget leave a spread session on the general kernel — the capacity sums and the statistics follow
+    if (buckets && !counts && c.gpu_strategy == KAI_SPREAD) buckets = false;
     bs.buckets = buckets ? (levels ? 3 : counts ? 2 : 1) : 0;
     if (sharded) { l.shard_mask_nrec(std::max(1, (c.NB * KAI_BLOCK + TB - 1) / TB), TB, c);
                    const int b0 = c.bt.n_lo / KAI_BLOCK, b1 = (c.bt.n_hi + KAI_BLOCK - 1) / KAI_BLOCK; (void)b0; (void)b1;

@@ -29,9 +29,9 @@
 using namespace kai;
 
 // The dynamic-LDS ceiling of a kernel (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the process and the device, not to a handle: a second handle with a smaller cluster
-// must not lower it under the first handle's next launch.  So the mark is kept per device for the whole process and only ever rises.  which: 0 k_fill_buckets, 1 k_fill_counts, 2 k_fill_levels.
+// must not lower it under the first handle's next launch.  So the mark is kept per device for the whole process and only ever rises.  which: 0 k_fill_buckets, 1 k_fill_counts, 2 k_fill_levels, 3 / 4 the spread instantiations of the latter two.
 static bool fill_dyn_raise(int device, int which, const void* kernel, size_t dyn) {
-    static std::mutex mu; static std::map<int, size_t> mark[3];
+    static std::mutex mu; static std::map<int, size_t> mark[5];
     std::lock_guard<std::mutex> lock(mu);
     size_t& m = mark[which][device];
     if (dyn <= m) return true;
@@ -325,15 +325,19 @@ struct DevLauncher {
     }
     void bucket_build(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_bucket_build, dim3(g), dim3(b), 0, core->stream, c); }
     void fill_counts(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {
-        if (!fill_dyn_raise(core->device, 1, reinterpret_cast<const void*>(k_fill_counts), dyn)) rc = KAI_ERR_HIP;
+        const bool sp = c.gpu_strategy == KAI_SPREAD;  // (the strategy is a compile-time parameter of the kernel's body: two instantiations)
+        if (!fill_dyn_raise(core->device, sp ? 3 : 1, reinterpret_cast<const void*>(sp ? k_fill_counts_spread : k_fill_counts), dyn)) rc = KAI_ERR_HIP;
         if (rp.mode == 0) (void)hipEventRecord(ev(1), core->stream);
-        hipLaunchKernelGGL(k_fill_counts, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
+        if (sp) hipLaunchKernelGGL(k_fill_counts_spread, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
+        else hipLaunchKernelGGL(k_fill_counts, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
         if (rp.mode != 1) (void)hipEventRecord(ev(2), core->stream);
     }
     void fill_levels(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {
-        if (!fill_dyn_raise(core->device, 2, reinterpret_cast<const void*>(k_fill_levels), dyn)) rc = KAI_ERR_HIP;
+        const bool sp = c.gpu_strategy == KAI_SPREAD;
+        if (!fill_dyn_raise(core->device, sp ? 4 : 2, reinterpret_cast<const void*>(sp ? k_fill_levels_spread : k_fill_levels), dyn)) rc = KAI_ERR_HIP;
         if (rp.mode == 0) (void)hipEventRecord(ev(1), core->stream);
-        hipLaunchKernelGGL(k_fill_levels, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
+        if (sp) hipLaunchKernelGGL(k_fill_levels_spread, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
+        else hipLaunchKernelGGL(k_fill_levels, dim3(g), dim3(b), dyn, core->stream, c, rp, bp);
         if (rp.mode != 1) (void)hipEventRecord(ev(2), core->stream);
     }
     void fill_buckets(int g, int b, size_t dyn, const KaiCtx& c, RoundParams rp, BucketParams bp) {

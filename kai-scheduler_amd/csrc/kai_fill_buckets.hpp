@@ -19,19 +19,23 @@
 // integer products).  Then whatever sequence of tasks lands on the node consumes at most idle0[r]·(devices consumed)/free0 of r, and a task that still finds
 // its devices finds its share of r (DESIGN.md §5.2b has the two-line proof).  Static predicates (class_fit, node readiness, worker labels, MIG / DRA rules)
 // are the okmask of the node records: a per-class bitmap ANDed into the lookup, dropped for classes it would not change.  Anything else — a node that fails
-// the proof, a spread or CPU-placed class, fractional or > 16 free devices, a node-sharded group — and the action runs on the general kernel (k_fill), with
+// the proof, a CPU-placed class, fractional or > 16 free devices, a node-sharded group — and the action runs on the general kernel (k_fill), with
 // identical results (tests/test_batch_path.py runs both against the oracle).
+// Spread classes (free / count descending: the HIGHEST level first) take the sets on the counting machines of kai_fill_counts.hpp / kai_fill_levels.hpp when every node with
+// a free device carries one device count; this one-wave kernel is bin-pack only.
 #pragma once
 #include "kai_batch.hpp"
 
 namespace kai {
 
 constexpr int KBK_GMAX = 16;  // levels the home arrays hold: free devices 1 .. 16
+constexpr int KBK_DIV_MAX = 1 << 22;  // spread: the largest divisor of the score (a node's device count) the sets take
 
 struct BucketMeta {        // written by k_bucket_build (zeroed by the host before it)
-    int32_t bad;           // != 0: the action does not qualify for the bucket fill (bit 0 class shape, 1 free amount, 2 a resource may bind first)
+    int32_t bad;           // != 0: the action does not qualify for the bucket fill (bit 0 class shape, 1 free amount, 2 a resource may bind first, 3 spread: a node with a free device whose divisor is no integer 1 .. KBK_DIV_MAX; more than one divisor: batch_bucket_params compares the two fields below)
     int32_t max_free;      // largest free amount of a live node
     int32_t live, pad;     // nodes some class may use
+    int32_t div_max, div_nmin;  // spread classes: the largest divisor of the spread score (NodeRec::cnt_gpu) among the live nodes with a free device, and KBK_DIV_MAX + 1 − the smallest one (0 / 0: no such node)
     int32_t ok_miss[64];   // class k: live nodes its static predicates turn away (0 = the class needs no bitmap of its own)
 };
 struct BucketParams { int32_t levels, nw, nw1, n_ok; int8_t okslot[64]; };  // okslot[k]: LDS slot of class k's static bitmap, -1 = none needed
@@ -43,10 +47,11 @@ KW_BODY void kb_bucket_build(const KaiCtx& c) {
     if (w >= NW) return;
     BucketMeta* meta = (BucketMeta*)b.bk_meta;
     int bad = 0;
-    if (w == 0 && lane < c.C) {  // class shape: bin-packed on the GPU, a whole number of 1 .. 16 devices, one pod slot
+    const bool spread = c.gpu_strategy == KAI_SPREAD;  // (every class placed on the GPU carries the session's gpu_strategy: a session is bin-pack or spread)
+    if (w == 0 && lane < c.C) {  // class shape: bin-packed or spread on the GPU, a whole number of 1 .. 16 devices, one pod slot
         const ClassRec cr = c.cls[lane];
         const double qd = cr.req[KAI_RES_GPU];
-        if (cr.cpu_only || cr.r_place != KAI_RES_GPU || cr.strategy != KAI_BINPACK || !(qd >= 1) || qd > KBK_GMAX || qd != (double)(int)qd) bad |= 1;
+        if (cr.cpu_only || cr.r_place != KAI_RES_GPU || cr.strategy != (spread ? KAI_SPREAD : KAI_BINPACK) || !(qd >= 1) || qd > KBK_GMAX || qd != (double)(int)qd) bad |= 1;
         if (c.R > KAI_RES_PODS && !(cr.req[KAI_RES_PODS] >= 1)) bad |= 1;  // the free-pod-slot predicate is implied only for classes that take a slot
     }
     const NodeRec rec = b.nrec[(size_t)w * KAI_BLOCK + lane];
@@ -70,6 +75,18 @@ KW_BODY void kb_bucket_build(const KaiCtx& c) {
                 const unsigned __int128 lhs = (unsigned __int128)(uint64_t)rq * (unsigned)fr, rhs = (unsigned __int128)(uint64_t)rec.idle[r] * (unsigned)q;
                 if (lhs > rhs) bad |= 4;
             }
+        }
+    }
+    if (spread) {
+        // spread orders the fitting nodes by free / cnt_gpu: the sets order them by free devices, which is the same order only while every node that can take a task divides by
+        // the same count.  An integer minimum and maximum over the wavefront, then over the grid; batch_bucket_params compares the two.
+        const bool has = live && fr >= 1;
+        const double dv = rec.cnt_gpu;
+        if (has && (!(dv >= 1) || dv > KBK_DIV_MAX || dv != (double)(int)dv)) bad |= 8;
+        if (kw::ballot(has && !(bad & 8))) {
+            int hi = has && !(bad & 8) ? (int)dv : 0, nlo = has && !(bad & 8) ? KBK_DIV_MAX + 1 - (int)dv : 0;
+            for (int l = 1; l < 64; l <<= 1) { const int a = kw::shfl(hi, lane ^ l), b2 = kw::shfl(nlo, lane ^ l); hi = a > hi ? a : hi; nlo = b2 > nlo ? b2 : nlo; }
+            if (lane == 0) { kw::atomic_max((int32_t*)&meta->div_max, hi); kw::atomic_max((int32_t*)&meta->div_nmin, nlo); }
         }
     }
     const uint64_t livew = kw::ballot(live);

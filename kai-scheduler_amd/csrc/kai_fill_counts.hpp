@@ -28,7 +28,10 @@ struct FcCmd { int32_t lv, k, per, tbase; };  // lv = g | g2 << 8: the first k n
 struct FcMove { int32_t w, cmd; uint64_t mask; };  // hand-over from the worker of the upper levels to the worker of the lower ones: the nodes `mask` of word w enter command cmd's target level (cmd bit 30: its last entry)
 struct FcLds { FcCmd ring[KFC_RING]; FcMove xring[KFC_RING]; int32_t cnt0[KBK_GMAX]; int32_t head, tail0, tail1, done, xhead, xtail, pad0, pad1; int64_t a_wait, b_idle[2], b_total[2]; };  // (the clocks: profiling)
 
-KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) {
+// SP: the classes' strategy on the GPU as a compile-time parameter (0 bin-pack, 1 spread).  Under spread a class's best node is the first node of the HIGHEST non-empty level g
+// (it fits iff g >= q) and takes one task before it moves to g − q; the capacity rule, the workers and the commands are the same.
+template <int SP>
+KW_BODY void kb_fill_counts_t(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     if (kb_round_off(c.bt)) return;
     KW_SHARED FcLds L;
     const BatchCtx& b = c.bt;
@@ -65,8 +68,8 @@ KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         int64_t pcy[4] = {0, 0, 0, 0};  // per job: decoding its parameters / deciding it and emitting its commands / its outcome; jobs
 #endif
         auto tails_min = [&]() { const int t0 = kw::lds_load_acq(&L.tail0); if (!two_workers) return t0; const int t1 = kw::lds_load_acq(&L.tail1); return t0 < t1 ? t0 : t1; };  // a slot is free once BOTH workers have read it
-        // the lowest non-empty level >= qc, 0 = none
-        #define KFC_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (qc) + __builtin_ctz(nz >> ((qc) - 1)) : 0)
+        // the lowest non-empty level >= qc (spread: the highest non-empty level, if it is >= qc), 0 = none
+        #define KFC_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (SP ? 32 - __builtin_clz(nz) : (qc) + __builtin_ctz(nz >> ((qc) - 1))) : 0)
         // k nodes leave level g for level g2 (0: none): the counts and the non-empty mask, from values this lane already holds
         #define KFC_MOVE(g, g2, k, cg) do { if (lane == (g) - 1) cnt -= (k); if ((cg) == (k)) nz &= ~(1u << ((g) - 1)); if ((g2) >= 1) { if (lane == (g2) - 1) cnt += (k); nz |= 1u << ((g2) - 1); } } while (0)
         // the 64 jobs of a stretch: one per lane; the NEXT stretch's loads are issued before this stretch is walked (a wavefront that waits out four HBM loads per 64 jobs waits ~3 ms per C5 cycle)
@@ -100,13 +103,14 @@ KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                     // place away) — else it places `cap` tasks, finds no node for the next one and is rolled back: cap + 1 decisions, the state it started from
                     const int qc = kw::bcast(q, ucls);
                     // the usual gang: all of it fits on the class's best node (its lowest non-empty level g holds nt·q devices) — one command, no capacity sum, no divisions
+                    // (spread: the first nt nodes of the top level take one task each — one command when that level holds nt nodes)
                     const int g0 = KFC_LEVEL_FOR(qc), need0 = nt * qc;
-                    if (g0 && need0 <= g0) {
+                    if (g0 && (SP ? nt >= 1 && nt <= kw::bcast(cnt, g0 - 1) : need0 <= g0)) {
                         if (wp - tail_seen >= KFC_RING) { kw::lds_store_rel(&L.head, wp); pub = wp; const int64_t w0 = kw::clock(); while (wp - tail_seen >= KFC_RING) { tail_seen = tails_min(); if (wp - tail_seen >= KFC_RING) kw::relax(); } a_wait += kw::clock() - w0; }
-                        const int cg = kw::bcast(cnt, g0 - 1), g2 = g0 - need0;
-                        if (lane == 0) { FcCmd cm; cm.lv = g0 | (g2 << 8); cm.k = 1; cm.per = nt; cm.tbase = first; L.ring[wp & (KFC_RING - 1)] = cm; }
+                        const int cg = kw::bcast(cnt, g0 - 1), g2 = SP ? g0 - qc : g0 - need0, k0 = SP ? nt : 1;
+                        if (lane == 0) { FcCmd cm; cm.lv = g0 | (g2 << 8); cm.k = k0; cm.per = SP ? 1 : nt; cm.tbase = first; L.ring[wp & (KFC_RING - 1)] = cm; }
                         wp++; steps++;
-                        KFC_MOVE(g0, g2, 1, cg);
+                        KFC_MOVE(g0, g2, k0, cg);
                         decisions += nt;
                         if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
                     } else {
@@ -118,9 +122,9 @@ KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) {
                         int done = 0;
                         while (done < nt) {
                             if (wp - tail_seen >= KFC_RING) { kw::lds_store_rel(&L.head, wp); pub = wp; const int64_t w0 = kw::clock(); while (wp - tail_seen >= KFC_RING) { tail_seen = tails_min(); if (wp - tail_seen >= KFC_RING) kw::relax(); } a_wait += kw::clock() - w0; }
-                            const int g = KFC_LEVEL_FOR(qc), r = bk_div_small(g, qc), rem = nt - done, cg = kw::bcast(cnt, g - 1);
+                            const int g = KFC_LEVEL_FOR(qc), r = SP ? 1 : bk_div_small(g, qc), rem = nt - done, cg = kw::bcast(cnt, g - 1);
                             int k = 1, per = rem;
-                            if (rem >= r) { per = r; k = bk_div_small(rem, r); if (k > cg) k = cg; }
+                            if (rem >= r) { per = r; k = SP ? rem : bk_div_small(rem, r); if (k > cg) k = cg; }
                             const int g2 = g - per * qc;
                             if (lane == 0) { FcCmd cm; cm.lv = g | (g2 << 8); cm.k = k; cm.per = per; cm.tbase = first + done; L.ring[wp & (KFC_RING - 1)] = cm; }
                             wp++; steps++;
@@ -256,8 +260,12 @@ KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     for (int i = tid; i < v.LV * v.NW; i += T) b.bk_words[i] = v.gw[i];
 }
 
+// the entry point picks the instantiation by the session's strategy on the GPU (the emulator's launchers call it; the device launches one of the two kernels below)
+KW_BODY void kb_fill_counts(const KaiCtx& c, RoundParams rp, BucketParams bp) { if (c.gpu_strategy == KAI_SPREAD) kb_fill_counts_t<1>(c, rp, bp); else kb_fill_counts_t<0>(c, rp, bp); }
+
 #if defined(__HIPCC__)
-__global__ void __launch_bounds__(256) k_fill_counts(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_counts(c, rp, bp); }
+__global__ void __launch_bounds__(256) k_fill_counts(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_counts_t<0>(c, rp, bp); }
+__global__ void __launch_bounds__(256) k_fill_counts_spread(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_counts_t<1>(c, rp, bp); }
 #endif
 
 }  // namespace kai

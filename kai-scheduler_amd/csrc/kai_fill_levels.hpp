@@ -80,7 +80,12 @@ KW_BODY void kfl_classify(FlStretch& s, int ucls, int qk, int capq) {
     s.todo = kw::ballot(s.valid && s.flag != BF_GATE && !s.is_def);
 }
 
-KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
+// SP: the classes' strategy on the GPU as a compile-time parameter (0 bin-pack, 1 spread).  Under spread every class's best node is the first node of the HIGHEST non-empty
+// level g (it fits iff g >= q) and takes ONE task before it moves to g − q: the command "(g, g − q, k = min(rest, nodes of g), per = 1)" — no quotient, no division.  The top
+// level strictly falls from step to step, capacities and the bookkeeper's replay are what they are under bin-pack.  Workers, bookkeeper, markers, the
+// command's format and the rings do not know the strategy.
+template <int SP>
+KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     if (kb_round_off(c.bt)) return;
     KW_SHARED FlLds L;
     const BatchCtx& b = c.bt;
@@ -129,8 +134,8 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
 #endif
         // the slowest reader's progress: lanes 0 .. LV − 1 the workers', lane LV the bookkeeper's
         auto tails_min = [&]() { int t = lane <= v.LV ? kw::lds_load_acq(&L.tail[lane < v.LV ? lane : KFL_LMAX]) : 0x7fffffff; for (int l = 1; l <= v.LV; l++) { const int o = kw::bcast(t, l); t = o < t ? o : t; } return kw::bcast(t, 0); };
-        // the lowest non-empty level >= qc, 0 = none
-        #define KFL_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (qc) + __builtin_ctz(nz >> ((qc) - 1)) : 0)
+        // the lowest non-empty level >= qc (spread: the highest non-empty level, if it is >= qc), 0 = none
+        #define KFL_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (SP ? 32 - __builtin_clz(nz) : (qc) + __builtin_ctz(nz >> ((qc) - 1))) : 0)
         // room for n more commands in the ring (a gang stays unpublished until its last task has found a level)
         #define KFL_ROOM(n) do { if (wp - tail_seen > KFL_RING - (n)) { kw::lds_store_rel(&L.head, wp); pub = wp; const int64_t w0 = kw::clock(); while (wp - tail_seen > KFL_RING - (n)) { tail_seen = tails_min(); if (wp - tail_seen > KFL_RING - (n)) kw::relax(); } a_wait += kw::clock() - w0; } } while (0)
         // lane 0 writes the command, the other lanes a copy into a slot of their own: one store, no branch.  jbits: the job's index within its stretch at bits 23-28 (for the bookkeeper)
@@ -148,13 +153,15 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
         // one step of a gang of ONE class, whole nodes: the lowest non-empty level g >= q holds r = g / q of its tasks per node; the first k nodes of it take r tasks each and move to
         // level g mod q, a remainder of fewer than r tasks goes to one node, which then stays at level g − rem·q.  No level: the step moves nothing and the gang has failed (it writes
         // a slot that stays unpublished: whatever its fields hold).
+        // Spread: g is the highest non-empty level (the highest set bit of nz; `ok` says g >= q), r = 1: the first k = min(rest of the gang, nodes of the level) nodes take one task
+        // each and move to g − q — no quotient table, no division.
         #define KFL_STEP(S, EMIT) \
             const uint32_t lv##S = nz >> (qc - 1); \
             ok = kw::nonzero01(lv##S);  /* a level >= q holds a node — as a number, not as a comparison (kai_simt.hpp) */ \
-            const int g##S = lv##S ? qc + __builtin_ctz(lv##S) : 0, gm1##S = g##S - 1; \
-            int r##S = (int)((tq >> ((4 * g##S - 4) & 31)) & 15u); r##S = r##S > 1 ? r##S : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
+            const int g##S = lv##S ? (SP ? 32 - __builtin_clz(nz) : qc + __builtin_ctz(lv##S)) : 0, gm1##S = g##S - 1; \
+            int r##S = SP ? 1 : (int)((tq >> ((4 * g##S - 4) & 31)) & 15u); r##S = r##S > 1 ? r##S : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
             const int rem##S = nt - placed; \
-            const int kq##S = (int)(((uint32_t)rem##S * (uint32_t)kw::bcast(invq, r##S - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
+            const int kq##S = SP ? rem##S : (int)(((uint32_t)rem##S * (uint32_t)kw::bcast(invq, r##S - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
             const int cg##S = kw::bcast(cnt, gm1##S & 63); \
             int k##S = kq##S < cg##S ? kq##S : cg##S; k##S = (k##S > 1 ? k##S : 1) * ok;  /* min(kq, nodes of the level), at least the one node; no level: nothing moves */ \
             const int per##S = r##S < rem##S ? r##S : rem##S, g2##S = g##S - per##S * qc; \
@@ -515,8 +522,12 @@ KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) {
     for (int i = tid; i < v.LV * v.NW; i += T) b.bk_words[i] = v.gw[i];
 }
 
+// the entry point picks the instantiation by the session's strategy on the GPU (the emulator's launchers call it; the device launches one of the two kernels below)
+KW_BODY void kb_fill_levels(const KaiCtx& c, RoundParams rp, BucketParams bp) { if (c.gpu_strategy == KAI_SPREAD) kb_fill_levels_t<1>(c, rp, bp); else kb_fill_levels_t<0>(c, rp, bp); }
+
 #if defined(__HIPCC__)
-__global__ void __launch_bounds__(64 * (KFL_LMAX + 2)) k_fill_levels(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_levels(c, rp, bp); }
+__global__ void __launch_bounds__(64 * (KFL_LMAX + 2)) k_fill_levels(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_levels_t<0>(c, rp, bp); }
+__global__ void __launch_bounds__(64 * (KFL_LMAX + 2)) k_fill_levels_spread(KaiCtx c, RoundParams rp, BucketParams bp) { kb_fill_levels_t<1>(c, rp, bp); }
 #endif
 
 }  // namespace kai
