@@ -14,7 +14,8 @@
 //     — one class, 1 .. KFL_SHORT tasks — runs through ≈ 70 instructions and two branches, everything but the counts in scalar registers, and stores nothing: the commands of a
 //     RUN of such gangs are held in lanes and written to the ring by all lanes at once when the run ends.
 //   * Wavefronts 1 .. L, the set workers: level g belongs to wavefront g, alone.  Its words, its two summaries and its first node are that wavefront's uniform state (the word that
-//     holds the first node is cached in registers: removing the level's first node — what every command does — reads nothing from LDS while that word lasts).  A worker looks at 64
+//     holds the first node is cached in registers: removing the level's first node — what every command does — reads nothing from LDS while that word lasts; the level's first summary lives in the wavefront's lanes, lane j the word of group j, so an emptied word costs one LDS read and an
+//     insertion none).  A worker looks at 64
 //     commands at a time, one per lane, and walks the ones that name its level: as the SOURCE it removes the level's first k nodes, writes the tasks' nodes and hands (word, mask) to
 //     the target level's worker through the ring of that (source, target) pair; as the TARGET it takes the nodes in when it reaches the command.  Every level sees its removals and
 //     insertions in command order; nodes only move DOWN the levels, so the wait-for graph has no cycle (a producer waits only for a consumer that is behind it; the worker that is
@@ -37,6 +38,9 @@ constexpr int KFL_XR = 32;                                 // entries of a hand-
 constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": it is walked in a run (its first two commands held in lanes; a third step sends it the long way)
 constexpr int KFL_JOB_SHIFT = 23;                          // a command's bits 23-28: its job's index within the stretch (or-ed in by the counting machine: kfl_cmd knows nothing of it)
 constexpr int KFL_PAIRS = KFL_LMAX * (KFL_LMAX - 1) / 2;   // (source level g, target level g2 < g)
+// -DKFL_PROF, a worker's clocks per kind of event: 0 one node leaves, its word stays | 1 one node, the word is emptied | 2 several nodes of one word | 3 several nodes over more than
+// one word | 4 nodes arrive in the cached word | 5 in an empty word | 6 in another non-empty word
+constexpr int KFL_WKINDS = 7;
 // a command, 8 bytes: bits 0-3 g, 4-7 g2, 8-11 per, 12-22 k | the upper word: tbase — the first k nodes of level g take `per` tasks each and move to level g2 (0: no level); their tasks are t_node[tbase ..)
 // A word with g = 0 is no command but a stretch's MARKER: the counting machine writes one in front of every stretch's commands.
 KW_BODY uint64_t kfl_cmd(int g, int g2, int k, int per, int tbase) { return (uint64_t)((uint32_t)g | ((uint32_t)g2 << 4) | ((uint32_t)per << 8) | ((uint32_t)k << 12)) | ((uint64_t)(uint32_t)tbase << 32); }
@@ -51,7 +55,13 @@ struct FlLds {
     int32_t tail[KFL_LMAX + 1];    // commands worker g (index g − 1) / the bookkeeper (index KFL_LMAX) has passed
     int32_t head, done, fin, b_dec;  // fin: jobs of the planned order the counting machine executed (for the bookkeeper's last stretch); b_dec: the bookkeeper's decisions
     int64_t w_idle[KFL_LMAX + 1], w_total[KFL_LMAX + 1];  // (the clocks: profiling)
+#ifdef KFL_PROF
+    int64_t wk_cyc[KFL_LMAX][KFL_WKINDS], wk_cnt[KFL_LMAX][KFL_WKINDS];  // a worker's cycles and events per kind of event
+#endif
 };
+#if defined(KFL_PROF) && defined(__HIPCC__)
+__device__ int64_t kfl_prof_workers[KFL_LMAX][KFL_WKINDS + 1][2];  // [level − 1][kind] = cycles, events; [level − 1][KFL_WKINDS] = idle, total (read by tools/micro/fill_bench.hip)
+#endif
 KW_BODY int kfl_pair(int g, int g2) { return (g - 1) * (g - 2) / 2 + (g2 - 1); }
 // a / b for 0 <= a <= 1024, 1 <= b <= 8 on the scalar unit: a·ceil(2^15 / b) >> 15 (the error a·(ceil − exact) / 2^15 stays below 1/32, the fraction of a / b below 7/8)
 KW_BODY int kfl_div(int a, int b) {
@@ -97,6 +107,9 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
     if (tid < KBK_GMAX) L.cnt0[tid] = 0;
     if (tid <= KFL_LMAX) { L.tail[tid] = 0; L.w_idle[tid] = 0; L.w_total[tid] = 0; }
     if (tid < KFL_PAIRS) L.xtail[tid] = 0;
+#ifdef KFL_PROF
+    if (tid < KFL_LMAX * KFL_WKINDS) { L.wk_cyc[tid / KFL_WKINDS][tid % KFL_WKINDS] = 0; L.wk_cnt[tid / KFL_WKINDS][tid % KFL_WKINDS] = 0; }
+#endif
     for (int i = tid; i < (KFL_PAIRS + 1) * KFL_XR; i += T) L.x[i / KFL_XR][i % KFL_XR].seq = 0;
     if (tid == 0) { L.head = 0; L.done = 0; L.fin = 0; L.b_dec = 0; }
     for (int i = tid; i < v.LV * v.NW; i += T) v.gw[i] = b.bk_words[i];
@@ -347,14 +360,26 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         // ------------------------------------------------------------------ wavefront G = 1 .. LV: the worker of level G.  Everything here is uniform over the wavefront.
         const int G = wave, lw = (G - 1) * v.NW, l1 = (G - 1) * v.NW1;
         KW_LDS_PTR(uint64_t) dm = (KW_LDS_PTR(uint64_t))&L.dummy[0];
-        uint64_t s2 = kw::ballot(lane < v.NW1 && v.s1[l1 + (lane < v.NW1 ? lane : 0)] != 0);  // second summary: bit j = the 64 words of group j hold a node
+        // the level's first summary in registers: lane j holds the word of group j (bit i: word 64 j + i holds a node; NW1 <= 64).  Only this worker reads and writes it and nobody
+        // wants it back, so after this load the s1 region of the LDS is not touched again: "the word is empty now" and "the word was empty" are lane writes.
+        uint64_t s1v = lane < v.NW1 ? v.s1[l1 + lane] : 0;
+        uint64_t s2 = kw::ballot(s1v != 0);  // second summary: bit j = the 64 words of group j hold a node
         int firstn = KB_INF, cw = -1; uint64_t curw = 0;  // the level's first node (lowest name rank), the word that holds it (index and current value)
-        auto first_of_group = [&](int w1, uint64_t m1) { cw = w1 * 64 + __builtin_ctzll(m1); curw = kfl_read(&v.gw[lw + cw]); firstn = (cw << 6) + __builtin_ctzll(curw); };
-        auto refill = [&]() { if (!s2) { firstn = KB_INF; cw = -1; curw = 0; return; } const int w1 = __builtin_ctzll(s2); first_of_group(w1, kfl_read(&v.s1[l1 + w1])); };
+        // the first node of the level from the summaries: one lane read, one LDS read
+        auto refill = [&]() { if (!s2) { firstn = KB_INF; cw = -1; curw = 0; return; } const int w1 = __builtin_ctzll(s2); cw = w1 * 64 + __builtin_ctzll(kw::bcast(s1v, w1)); curw = kfl_read(&v.gw[lw + cw]); firstn = (cw << 6) + __builtin_ctzll(curw); };
         refill();
         // lane t: this worker's hand-over ring to level t + 1 — entries written, the consumer's progress as last read; lane s: its ring from level s + 1 — entries taken
         int xp = 0, xseen = 0, xc = 0;
         int tail = 0; int64_t w_idle = 0; const int64_t w_start = kw::clock();
+#ifdef KFL_PROF
+        // the clocks per kind of event (tools/micro/fill_bench.hip -DKFL_PROF): cycles and events, kept by lane 0 in the LDS; the product build carries none of it
+        int64_t wt = kw::clock();
+        #define KFL_WT0() (wt = kw::clock())
+        #define KFL_WK(kind_) do { const int64_t n_ = kw::clock(); if (lane == 0) { L.wk_cyc[G - 1][kind_] += n_ - wt; L.wk_cnt[G - 1][kind_]++; } wt = n_; } while (0)
+#else
+        #define KFL_WT0() (void)0
+        #define KFL_WK(kind_) (void)0
+#endif
         for (;;) {
             const int head = kfl_load(&L.head);
             if (tail == head) {
@@ -368,62 +393,88 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                 const uint64_t mc = L.ring[(tail + lane) & (KFL_RING - 1)];  // (lanes beyond the batch read a slot that is not used)
                 uint64_t mine = kw::ballot(lane < nb && ((int)(mc & 15) == G || (int)((mc >> 4) & 15) == G));
                 while (mine) {
+                    KFL_WT0();
                     const int ci = __builtin_ctzll(mine); mine &= mine - 1;
                     const int ca = kw::bcast((int)(uint32_t)mc, ci);
                     const int g = ca & 15, g2 = (ca >> 4) & 15;
                     if (g == G) {
-                        // SOURCE: the level's first k nodes leave it, `per` tasks on each
+                        // SOURCE: the level's first k nodes leave it, `per` tasks on each.  Every LDS store goes through a pointer that is lane 0's target or the lane's own dummy slot.
                         const int per = (ca >> 8) & 15; int left = (ca >> 12) & 0x7ff, tb = kw::bcast((int)(uint32_t)(mc >> 32), ci);
                         const int pr = g2 >= 1 ? kfl_pair(G, g2) : KFL_PAIRS;  // (no level: the ring nobody reads)
+                        const int xl = (g2 - 1) & 63;                          // (no level: lane 63, which is never counted up)
+#ifdef KFL_PROF
+                        const int k_all = left; int n_words = 0, n_emptied = 0;
+#endif
                         if (__builtin_expect(left == 1, 1)) {
                             // the usual command, straight through: ONE node, the level's first, leaves with `per` tasks on it; the word it sat in stays non-empty and the hand-over ring has
-                            // room (either of the two failing: one rarely taken exit each).  Every LDS store goes through a pointer that is lane 0's target or the lane's own dummy slot.
+                            // room (either of the two failing: one rarely taken exit each).  The replay has this path at 435 cycles against 806 through the ballot below (profiles/r12).
                             const int w = cw; const uint64_t mask = curw & (0 - curw), neww = curw ^ mask;
                             b.t_node[tb + (lane < per ? lane : per - 1)] = firstn;  // (its tasks all sit on it, per <= 8; the lanes beyond them store the last one's again: no branch)
                             kfl_write(&v.gw[lw + w], neww, dm);
-                            const int xl = (g2 - 1) & 63, n_w = kw::bcast(xp, xl);  // (no level: lane 63, which is never counted up)
+                            const int n_w = kw::bcast(xp, xl);
                             if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
                             KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
                             e->mask = mask; e->w = w | (1 << 30);
                             kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
                             xp += lane == g2 - 1 ? 1 : 0;
                             if (__builtin_expect(neww != 0, 1)) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
-                            else {  // the word is empty: its bit in the first summary goes, and the level's first node is the first node of the next word
-                                const int w1 = w >> 6; const uint64_t m1 = kfl_read(&v.s1[l1 + w1]) & ~(1ull << (w & 63));
-                                kfl_write(&v.s1[l1 + w1], m1, dm);
-                                if (m1) first_of_group(w1, m1); else { s2 &= ~(1ull << w1); refill(); }
+                            else {
+                                const int w1 = w >> 6; const uint64_t m1 = kw::bcast(s1v, w1) & ~(1ull << (w & 63));
+                                s1v = kw::writelane(s1v, m1, w1);
+                                s2 &= ~((uint64_t)(uint32_t)(1 - kw::nonzero01((uint32_t)m1 | (uint32_t)(m1 >> 32))) << w1);
+                                refill();
+#ifdef KFL_PROF
+                                n_emptied++;
+#endif
                             }
                             left = 0;
                         }
-                        while (left > 0) {
+                        while (__builtin_expect(left > 0, 0)) {
+                            // several nodes, word by word, each word straight through: the first m = min(nodes left, nodes of the cached word) nodes of the word that holds the level's
+                            // first node are picked by ONE ballot (lane i ranks bit i of the word), the lanes that hold them write their tasks' nodes, and (word, mask) is handed over in
+                            // one entry.  No loop over the nodes, none over the bits; a command whose nodes span words comes round again for the next word.
                             const int w = cw; const uint64_t word = curw;
-                            int m = 1; uint64_t mask = word & (0 - word);
-                            if (left > 1) {  // several nodes: the set bits of the first node's word, from it upwards
-                                m = __builtin_popcountll(word); mask = word;
-                                if (m > left) { m = left; mask = 0; uint64_t x = word; for (int j = 0; j < m; j++) { mask |= x & (0 - x); x &= x - 1; } }
-                                for (int t0 = 0; t0 < m * per; t0 += 64) {  // task t of this word's share sits on the (t / per)-th node of the mask
-                                    const int t = t0 + lane;
-                                    if (t < m * per) { uint64_t mm = mask; for (int j = bk_div_small(t, per); j > 0; j--) mm &= mm - 1; b.t_node[tb + t] = (w << 6) + __builtin_ctzll(mm); }
-                                }
-                            } else if (lane < per) b.t_node[tb + lane] = firstn;  // one node (the usual command): its tasks all sit on it (per <= 8)
-                            const uint64_t neww = word ^ mask;
+                            const int pop = __builtin_popcountll(word), m = left < pop ? left : pop;
+                            const int r = kw::rank_below(word);
+                            const bool sel = ((word >> lane) & 1ull) != 0 && r < m;
+                            const uint64_t mask = kw::ballot(sel), neww = word ^ mask;
+                            // the tasks' nodes, unpredicated: the lane of the node of rank r stores it for the tasks r·per .. r·per + per − 1 (a uniform loop over per <= 8), every other
+                            // lane stores the word's last node for its last task again.  One node: its tasks' lanes store it (lanes < per; the lanes beyond them the last one's again).
+                            const int one = m == 1, lastn = (w << 6) + 63 - __builtin_clzll(mask);
+                            const int val = sel ? (w << 6) + lane : lastn;
+                            const int onem = 0 - one, off1 = lane < per ? lane : per - 1, offm = sel ? r * per : m * per - 1;  // (selected by masks: no branch on `one`)
+                            int a = tb + ((off1 & onem) | (offm & ~onem));
+                            b.t_node[a] = val;
+                            if (__builtin_expect((per & ~onem) > 1, 0)) {  // several nodes with several tasks each: the tasks behind a node's first
+                                const int stp = sel ? 1 : 0;
+                                _Pragma("nounroll") for (int j = 1; j < per; j++) { a += stp; b.t_node[a] = val; }
+                            }
                             kfl_write(&v.gw[lw + w], neww, dm);
-                            if (neww) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
-                            else {  // the word is empty: its bit in the first summary goes, and the level's first node is the first node of the next word
-                                const int w1 = w >> 6; const uint64_t m1 = kfl_read(&v.s1[l1 + w1]) & ~(1ull << (w & 63));
-                                kfl_write(&v.s1[l1 + w1], m1, dm);
-                                if (m1) first_of_group(w1, m1); else { s2 &= ~(1ull << w1); refill(); }
-                            }
                             left -= m; tb += m * per;
-                            if (g2 >= 1) {  // hand the nodes over to the worker of the target level
-                                const int n_w = kw::bcast(xp, g2 - 1);
-                                if (n_w - kw::bcast(xseen, g2 - 1) >= KFL_XR) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == g2 - 1) xseen = t; }
-                                const int sl = n_w & (KFL_XR - 1);
-                                if (lane == 0) { L.x[pr][sl].mask = mask; L.x[pr][sl].w = w | (left == 0 ? 1 << 30 : 0); }
-                                kw::lds_store_ordered(&L.x[pr][sl].seq, n_w + 1);
-                                if (lane == g2 - 1) xp++;
+                            // one entry for the target level's worker
+                            const int n_w = kw::bcast(xp, xl);
+                            if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
+                            KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
+                            e->mask = mask; e->w = w | (left == 0 ? 1 << 30 : 0);
+                            kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
+                            xp += lane == g2 - 1 ? 1 : 0;
+                            if (__builtin_expect(neww != 0, 1)) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
+                            else {  // the word is empty: its bit in the first summary goes (a lane write), and the level's first node is the first node of the next word
+                                const int w1 = w >> 6; const uint64_t m1 = kw::bcast(s1v, w1) & ~(1ull << (w & 63));
+                                s1v = kw::writelane(s1v, m1, w1);
+                                s2 &= ~((uint64_t)(uint32_t)(1 - kw::nonzero01((uint32_t)m1 | (uint32_t)(m1 >> 32))) << w1);  // (the group's bit goes with its last word — as a number, not as a comparison)
+                                refill();
+#ifdef KFL_PROF
+                                n_emptied++;
+#endif
                             }
+#ifdef KFL_PROF
+                            n_words++;
+#endif
                         }
+#ifdef KFL_PROF
+                        if (k_all == 1) { if (n_emptied) KFL_WK(1); else KFL_WK(0); } else if (n_words == 1) KFL_WK(2); else KFL_WK(3);
+#endif
                     } else {
                         // TARGET: take the command's nodes in as the source level's worker hands them over
                         const int pr = kfl_pair(g, G);
@@ -433,19 +484,28 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                             // the sequence number, then the entry behind it, in one trip to the LDS: the LDS serves a wavefront's reads in issue order and the producer stored the number last
                             // (the reads of the entry are atomic ones so that the compiler leaves them in front of the test)
                             int sq = kw::lds_load_ordered(&L.x[pr][sl].seq), wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); uint64_t mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask);
-                            if (__builtin_expect(kw::uni(sq) != n_r + 1, 0)) { const int64_t i0 = kw::clock(); while (kfl_load(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask); }
+                            if (__builtin_expect(kw::uni(sq) != n_r + 1, 0)) { const int64_t i0 = kw::clock(); while (kfl_load(&L.x[pr][sl].seq) != n_r + 1) kw::relax(); w_idle += kw::clock() - i0; wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask); KFL_WT0(); }
                             const int wf = kw::bcast(wf_v, 0), w = wf & 0x3fffffff; const uint64_t mask = kw::bcast(mk_v, 0);
                             last = (wf >> 30) & 1;
                             kw::lds_store_ordered(&L.xtail[pr], n_r + 1);
                             if (lane == g - 1) xc++;
-                            if (w == cw) { curw |= mask; kfl_write(&v.gw[lw + w], curw, dm); firstn = (w << 6) + __builtin_ctzll(curw); }
+                            if (w == cw) { curw |= mask; kfl_write(&v.gw[lw + w], curw, dm); firstn = (w << 6) + __builtin_ctzll(curw); KFL_WK(4); }
                             else {
-                                const uint64_t old = kfl_read(&v.gw[lw + w]), nw = old | mask;
-                                kfl_write(&v.gw[lw + w], nw, dm);
-                                if (!old) { const int w1 = w >> 6; const uint64_t o1 = kfl_read(&v.s1[l1 + w1]); kfl_write(&v.s1[l1 + w1], o1 | (1ull << (w & 63)), dm); if (!o1) s2 |= 1ull << w1; }
+                                // another word: the bits go in with an LDS `or` that returns nothing (one writer per level: a store that merges), the first summary is told in a lane —
+                                // nothing is read.  A node below the level's first one makes its word the cached one; that word was EMPTY (a non-empty word other than the cached one
+                                // lies above it, and so does every node of it), so its value is the entry's mask.  An empty level is the same case: every node lies below KB_INF.
+                                const int w1 = w >> 6;
+#ifdef KFL_PROF
+                                const bool was_empty = ((kw::bcast(s1v, w1) >> (w & 63)) & 1ull) == 0;
+#endif
+                                { KW_LDS_PTR(uint64_t) q = lane == 0 ? (KW_LDS_PTR(uint64_t))&v.gw[lw + w] : dm + lane; kw::lds_or(q, mask); }
+                                s1v = kw::writelane(s1v, kw::bcast(s1v, w1) | (1ull << (w & 63)), w1); s2 |= 1ull << w1;
                                 const int n = (w << 6) + __builtin_ctzll(mask), fn = kw::uni(firstn);
-                                const bool lower = n < fn;  // (every node the word held before lies at or above the old first node)
-                                firstn = lower ? n : fn; cw = lower ? w : cw; curw = lower ? nw : curw;
+                                const bool lower = n < fn;
+                                firstn = lower ? n : fn; cw = lower ? w : cw; curw = lower ? mask : curw;
+#ifdef KFL_PROF
+                                if (was_empty) KFL_WK(5); else KFL_WK(6);
+#endif
                             }
                         }
                     }
@@ -454,6 +514,8 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
             }
             kw::lds_store_rel(&L.tail[G - 1], tail);
         }
+        #undef KFL_WT0
+        #undef KFL_WK
         if (lane == 0) { L.w_idle[G - 1] = w_idle; L.w_total[G - 1] = kw::clock() - w_start; }
     } else if (wave == v.LV + 1) {
         // ------------------------------------------------------------------ wavefront LV + 1: the bookkeeper.  It replays the commands on the capacities (lane q − 1: capq) and books,
@@ -512,6 +574,9 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
     kw::sync();
     if (tid == 0) {
         b.fs[0].decisions += L.b_dec;
+#if defined(KFL_PROF) && defined(__HIPCC__)
+        for (int l = 0; l < KFL_LMAX; l++) { for (int k = 0; k < KFL_WKINDS; k++) { kfl_prof_workers[l][k][0] = L.wk_cyc[l][k]; kfl_prof_workers[l][k][1] = L.wk_cnt[l][k]; } kfl_prof_workers[l][KFL_WKINDS][0] = L.w_idle[l]; kfl_prof_workers[l][KFL_WKINDS][1] = L.w_total[l]; }
+#endif
 #ifndef KFL_PROF
         // the readers' clocks: idle and total summed, the busiest one's busy cycles and its level (9 = the bookkeeper)
         int64_t idle = 0, total = 0, busy = 0; int lvl = 0;

@@ -46,6 +46,9 @@ KW_DEV uint64_t uni(uint64_t v) { return ((uint64_t)(uint32_t)__builtin_amdgcn_r
 // (clang has no __builtin for it: the declaration binds the name to the compiler's own intrinsic, as the HIP headers do for theirs)
 extern "C" __device__ int kw_llvm_writelane(int v, int dst, int old) __asm("llvm.amdgcn.writelane.i32");
 KW_DEV int writelane(int old, int v, int dst) { return kw_llvm_writelane(__builtin_amdgcn_readfirstlane(v), __builtin_amdgcn_readfirstlane(dst), old); }
+KW_DEV uint64_t writelane(uint64_t old, uint64_t v, int dst) { return ((uint64_t)(uint32_t)writelane((int)(old >> 32), (int)(v >> 32), dst) << 32) | (uint32_t)writelane((int)old, (int)v, dst); }
+// the set bits of the uniform m below the calling lane (v_mbcnt_lo / v_mbcnt_hi): the lane's rank among the lanes m names
+KW_DEV int rank_below(uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 // v != 0 as the number 0 / 1 for a uniform v (the same in every lane), in ONE scalar instruction the compiler knows nothing about: a truth value that is selected on, multiplied with and
 // added up comes back from the compiler as a lane mask, a vector select and a read back into a scalar register (30 cycles on a chain of dependent instructions)
 KW_DEV int nonzero01(uint32_t v) { int r; asm("s_min_u32 %0, %1, 1" : "=s"(r) : "s"(v) : "scc"); return r; }
@@ -70,6 +73,8 @@ KW_DEV void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 KW_DEV void lds_order() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 // read-modify-write of one LDS word in ONE ds instruction (ds_xor_rtn_b64); returns the old value.  Wavefront scope: the word belongs to the calling lane
 KW_DEV uint64_t lds_xor(KW_LDS_PTR(uint64_t) p, uint64_t v) { return __hip_atomic_fetch_xor(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+// bits merged into one LDS word without reading it back (ds_or_b64, nothing returned): a store that keeps what the word held.  Wavefront scope: the word has one writer
+KW_DEV void lds_or(KW_LDS_PTR(uint64_t) p, uint64_t v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
 KW_DEV void expect_uniform(long long) {}
 KW_DEV void fence_wg() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
 // two wavefronts of one workgroup hand data over through LDS (kai_fill_counts.hpp: a command ring): the producer's stores, then its release store of the counter; the consumer's
@@ -235,6 +240,8 @@ inline uint64_t wave_max_u64(uint64_t v, int line = __builtin_LINE()) {
 template <class T> inline T bcast(T v, int src, int line = __builtin_LINE()) { return shfl(v, src, line); }
 template <class T> inline T uni(T v) { return v; }  // (the lanes hold the same value by contract; expect_uniform() checks one where a doubt needs settling)
 inline int writelane(int old, int v, int dst) { return lane() == dst ? v : old; }
+inline uint64_t writelane(uint64_t old, uint64_t v, int dst) { return lane() == dst ? v : old; }
+inline int rank_below(uint64_t m) { return __builtin_popcountll(m & ((1ull << lane()) - 1)); }
 inline int nonzero01(uint32_t v) { return v ? 1 : 0; }
 inline uint64_t opaque(uint64_t v) { return v; }
 template <int P> inline void set_prio() {}
@@ -259,6 +266,7 @@ inline void relax(int line = __builtin_LINE()) { wave_bar(line); }  // the whole
 inline void wave_sync(int line = __builtin_LINE()) { wave_bar(line); }
 inline void lds_order(int line = __builtin_LINE()) { wave_bar(line); }
 inline uint64_t lds_xor(uint64_t* p, uint64_t v) { const uint64_t o = *p; *p = o ^ v; return o; }
+inline void lds_or(uint64_t* p, uint64_t v) { *p |= v; }
 // debug aid: every lane must hold the same value here (a branch on it is meant to be uniform)
 inline void expect_uniform(long long v, int line = __builtin_LINE()) { const long long v0 = shfl(v, 0, line); if (v != v0) { std::fprintf(stderr, "kw: value not uniform at line %d: lane %d has %lld, lane 0 has %lld\n", line, lane(), v, v0); std::abort(); } }  // the emulator's lanes are fibers: they meet here
 }  // namespace kw

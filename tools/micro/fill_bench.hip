@@ -2,7 +2,8 @@
 // A development aid for the fill kernels (the product library takes ≈ 7 min to build; this file a few seconds): the dump holds the planned order of a round, the sets before the launch
 // and — from the emulated kernel, which the scalar C++ shadow and the oracle vouch for — every output, all of which are compared here.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o tools/micro/fill_bench tools/micro/fill_bench.hip
-//   tools/micro/fill_bench tools/micro/data/c5_2 [reps]
+//   tools/micro/fill_bench tools/micro/data/c5_2 [reps] [spread]      (spread: the dump of a session that spreads its GPU classes — the spread instantiations, no k_fill_buckets)
+// -DKFL_PROF (tools/micro/fill_bench_prof): the counting machine's phase clocks and, per level, the set worker's cycles and events per kind of event.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -22,7 +23,7 @@ template <class T> static void rd(FILE* f, std::vector<T>& v, size_t n) { v.resi
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: fill_bench <dump prefix> [reps]\n"); return 2; }
-    const std::string pre = argv[1]; const int reps = argc > 2 ? std::atoi(argv[2]) : 5;
+    const std::string pre = argv[1]; const int reps = argc > 2 ? std::atoi(argv[2]) : 5; const bool spread = argc > 3 && !std::strcmp(argv[3], "spread");
     FILE* f = std::fopen((pre + ".in").c_str(), "rb"); if (!f) { std::perror("in"); return 2; }
     int32_t hdr[16]; RoundParams rp; BucketParams bp;
     if (std::fread(hdr, 4, 16, f) != 16 || std::fread(&rp, sizeof rp, 1, f) != 1 || std::fread(&bp, sizeof bp, 1, f) != 1 || hdr[0] != 0x4b464c31) { std::fprintf(stderr, "bad header\n"); return 2; }
@@ -40,7 +41,7 @@ int main(int argc, char** argv) {
     std::vector<ClassRec> cls(64); for (int k = 0; k < 64; k++) { std::memset(&cls[k], 0, sizeof(ClassRec)); cls[k].req[KAI_RES_GPU] = qd[k]; }
     std::vector<int32_t> q_valid(Q + 1, 0); q_valid[Q] = V;
     KaiCtx c; std::memset((void*)&c, 0, sizeof c);
-    c.C = C; c.Q = Q; c.P = P; c.NB = NW;
+    c.C = C; c.Q = Q; c.P = P; c.NB = NW; c.gpu_strategy = spread ? KAI_SPREAD : KAI_BINPACK;
     c.cls = (KAI_GP(const ClassRec))dev(cls);
     BatchCtx& b = c.bt;
     b.q_valid = (KAI_GP(int32_t))dev(q_valid);
@@ -56,10 +57,13 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_levels), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_counts), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_buckets), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_levels_spread), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fill_counts_spread), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     const char* names[3] = {"k_fill_levels", "k_fill_counts", "k_fill_buckets"};
     for (int kern = 0; kern < 3; kern++) {
         if (kern == 0 && LV > KFL_LMAX) continue;
+        if (kern == 2 && spread) continue;
         if (const char* only = std::getenv("FILL_BENCH_ONLY")) if (std::atoi(only) != kern) continue;
         double best = 1e30, sum = 0; FillStatus fs{};
         for (int r = 0; r < reps; r++) {
@@ -67,7 +71,9 @@ int main(int argc, char** argv) {
             CK(hipMemset(d_node, 0xff, (size_t)P * 4)); CK(hipMemset(d_fs, 0, sizeof(FillStatus)));
             CK(hipDeviceSynchronize());
             CK(hipEventRecord(e0, 0));
-            if (kern == 0) hipLaunchKernelGGL(k_fill_levels, dim3(1), dim3(64 * (LV + 2)), dyn, 0, c, rp, bp);
+            if (kern == 0 && spread) hipLaunchKernelGGL(k_fill_levels_spread, dim3(1), dim3(64 * (LV + 2)), dyn, 0, c, rp, bp);
+            else if (kern == 0) hipLaunchKernelGGL(k_fill_levels, dim3(1), dim3(64 * (LV + 2)), dyn, 0, c, rp, bp);
+            else if (kern == 1 && spread) hipLaunchKernelGGL(k_fill_counts_spread, dim3(1), dim3(256), dyn, 0, c, rp, bp);
             else if (kern == 1) hipLaunchKernelGGL(k_fill_counts, dim3(1), dim3(256), dyn, 0, c, rp, bp);
             else hipLaunchKernelGGL(k_fill_buckets, dim3(1), dim3(256), dyn, 0, c, rp, bp);
             CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
@@ -89,6 +95,17 @@ int main(int argc, char** argv) {
         std::printf("%-15s best %8.3f ms  mean %8.3f ms  | executed %d decisions %lld committed %lld commands %lld | counting-wave cycles %lld (waited for the ring %lld) workers idle %lld / total %lld, busiest busy %lld (level %lld) | %s (%lld differences)\n",
                     names[kern], best, sum / reps, fs.n_done, (long long)fs.decisions, (long long)fs.committed, (long long)fs.rescans2, (long long)fs.cycles_total, (long long)fs.cycles_load,
                     (long long)fs.cycles_update, (long long)fs.cycles_rescan, (long long)fs.block_loads, (long long)fs.rescans1, bad ? "DIFFERS from the dump" : "outputs = the dump's", bad);
+#ifdef KFL_PROF
+        if (kern == 0) {  // the set workers' clocks of the last repetition: cycles / events per kind, then idle and total
+            int64_t wk[KFL_LMAX][KFL_WKINDS + 1][2]; CK(hipMemcpyFromSymbol(wk, HIP_SYMBOL(kfl_prof_workers), sizeof wk));
+            const char* kinds[KFL_WKINDS] = {"one node, word stays", "one node, word emptied", "several nodes, one word", "several nodes, more words", "into the cached word", "into an empty word", "into another non-empty word"};
+            for (int l = 0; l < LV; l++) {
+                std::printf("  worker of level %d: idle %lld of %lld cycles |", l + 1, (long long)wk[l][KFL_WKINDS][0], (long long)wk[l][KFL_WKINDS][1]);
+                for (int k = 0; k < KFL_WKINDS; k++) std::printf(" %s: %lld cycles / %lld events (%lld each) |", kinds[k], (long long)wk[l][k][0], (long long)wk[l][k][1], (long long)(wk[l][k][1] ? wk[l][k][0] / wk[l][k][1] : 0));
+                std::printf("\n");
+            }
+        }
+#endif
     }
     return 0;
 }
