@@ -11,8 +11,13 @@
 //     and ring position) having booked the tasks it placed + 1 decisions, exactly what the capacity rule of kai_fill_counts.hpp books.  So this wavefront keeps no
 //     capacities at all.  Outcomes, Statement numbers and operation offsets of a stretch come out of one ballot and one prefix sum at its end.  A command is 8 bytes.
 //     This wavefront's chain of dependent instructions is the kernel's length, so the walk is written for the instruction stream it compiles to: the usual gang
-//     — one class, 1 .. KFL_SHORT tasks — runs through ≈ 70 instructions and two branches, everything but the counts in scalar registers, and stores nothing: the commands of a
-//     RUN of such gangs are held in lanes and written to the ring by all lanes at once when the run ends.
+//     — one class, 1 .. KFL_SHORT tasks — runs through 31 instructions and two branches, everything but the counts in scalar registers, and stores nothing: the commands of a
+//     RUN of such gangs are held in lanes and written to the ring by all lanes at once when the run ends.  What a gang's first step is but for the level's population — the
+//     level, the target level, the tasks per node, the nodes it wants, whether that is all of it, whether that is what the plan predicted — is a pure function of the job and
+//     of the mask of non-empty levels, so all 64 lanes work it out at once for their own jobs, as one word each: the DECISION TABLE.  The gang reads its word (one lane read),
+//     takes k = min(kq, nodes of the level), holds the command, writes two counts and two bits of the mask; one test sends it out of line when that was not all of the gang
+//     (the general step, unchanged) or when the mask is no longer the one the table was built for — then the table is rebuilt before the next gang reads its word.  No gang is
+//     decided before the counts and the mask it sees are final.  The run is cut in front of the first job whose word says "not as predicted", so the loop tests nothing for it.
 //   * Wavefronts 1 .. L, the set workers: level g belongs to wavefront g, alone.  Its words, its two summaries and its first node are that wavefront's uniform state (the word that
 //     holds the first node is cached in registers: removing the level's first node — what every command does — reads nothing from LDS while that word lasts; the level's first summary lives in the wavefront's lanes, lane j the word of group j, so an emptied word costs one LDS read and an
 //     insertion none).  A worker looks at 64
@@ -125,17 +130,18 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
     const int wave = kw::uni(tid >> 6);  // (the compiler takes anything computed from the thread's number for different in every lane: told otherwise, a wavefront's role, its level and its tests sit on the scalar unit)
     if (wave == 0) {
         // ------------------------------------------------------------------ wavefront 0: the counting machine.
-        // lane l: cnt = nodes of level l + 1 (lane 63: nodes that left for no level, see KFL_EVENT).  lane q − 1: tab = the quotients g / q.  lane k: qk = devices class k asks for.
+        // lane g: cnt = nodes of level g (lane 0: nodes that left for no level, see KFL_EVENT — a command's g and g2 are lane numbers as they stand).  lane q − 1: tab = the quotients
+        // g / q.  lane k: qk = devices class k asks for.
         // lane b − 1: invq = ceil(2^15 / b), the table of kfl_div (b = 1: a·2^15 >> 15 = a, so the step divides without asking whether it has to).
 #ifdef KFL_PRIO
         kw::set_prio<KFL_PRIO>();  // (an experiment on placement, DESIGN.md 5.2d: no gain measured, off in the product)
 #endif
-        int cnt = lane < v.LV ? L.cnt0[lane] : 0;
+        int cnt = lane >= 1 && lane <= v.LV ? L.cnt0[lane - 1] : 0;
         const bool act = lane < C;
         const int qk = act ? (int)c.cls[lane].req[KAI_RES_GPU] : 0x7fffffff;
         const uint32_t tab = kfl_tab(lane, v.LV);
         const int invq = (int)(((lane < 4 ? 0x2000'2AAB'4000'8000ull : 0x1000'124A'1556'199Aull) >> (16 * (lane & 3))) & 0xffff);
-        uint32_t nz = (uint32_t)kw::ballot(cnt > 0);  // bit l: level l + 1 holds a node
+        uint32_t nz = (uint32_t)kw::ballot(cnt > 0) | 1u;  // bit g: level g holds a node (bit 0, "no level", is always set: a node that leaves for no level sets it again)
         int decisions = 0, attempted = 0, committed = 0, rollbacks = 0, ops = 0, n_done = rp.start, mismatch = 0;
         int wp = 0, tail_seen = 0, pub = 0, n_mark = 0;  // commands written (the stretches' markers, n_mark, among them) / the slowest reader's progress as last read / commands published (per 64 commands and at the end of a stretch)
         int64_t a_wait = 0;               // cycles this wavefront waited for room in the ring
@@ -148,34 +154,32 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         // the slowest reader's progress: lanes 0 .. LV − 1 the workers', lane LV the bookkeeper's
         auto tails_min = [&]() { int t = lane <= v.LV ? kw::lds_load_acq(&L.tail[lane < v.LV ? lane : KFL_LMAX]) : 0x7fffffff; for (int l = 1; l <= v.LV; l++) { const int o = kw::bcast(t, l); t = o < t ? o : t; } return kw::bcast(t, 0); };
         // the lowest non-empty level >= qc (spread: the highest non-empty level, if it is >= qc), 0 = none
-        #define KFL_LEVEL_FOR(qc) ((nz >> ((qc) - 1)) ? (SP ? 32 - __builtin_clz(nz) : (qc) + __builtin_ctz(nz >> ((qc) - 1))) : 0)
+        #define KFL_LEVEL_FOR(qc) (((nz >> 1) >> ((qc) - 1)) ? (SP ? 31 - __builtin_clz(nz) : (qc) + __builtin_ctz((nz >> 1) >> ((qc) - 1))) : 0)
         // room for n more commands in the ring (a gang stays unpublished until its last task has found a level)
         #define KFL_ROOM(n) do { if (wp - tail_seen > KFL_RING - (n)) { kw::lds_store_rel(&L.head, wp); pub = wp; const int64_t w0 = kw::clock(); while (wp - tail_seen > KFL_RING - (n)) { tail_seen = tails_min(); if (wp - tail_seen > KFL_RING - (n)) kw::relax(); } a_wait += kw::clock() - w0; } } while (0)
         // lane 0 writes the command, the other lanes a copy into a slot of their own: one store, no branch.  jbits: the job's index within its stretch at bits 23-28 (for the bookkeeper)
         #define KFL_EMIT(g_, g2_, k_, per_, tb_) do { KW_LDS_PTR(uint64_t) sl_ = lane == 0 ? (KW_LDS_PTR(uint64_t))&L.ring[wp & (KFL_RING - 1)] : (KW_LDS_PTR(uint64_t))&L.dummy[lane]; *sl_ = kfl_cmd(g_, g2_, k_, per_, tb_) | jbits; wp++; } while (0)
-        // k nodes leave level g, which holds cg >= k, for level g2 (0: none): two lanes of the counts are written, two bits of the non-empty mask change (bit g − 1 goes when the level
-        // is emptied, bit g2 − 1 comes) — all of it on the scalar unit.  Nodes that leave for no level are counted in lane 63, which nobody reads; a step without a level (g = 0,
-        // k = 0, g2 <= 0) changes no lane, and the gang it belongs to is rolled back.
-        // (Truth values are kept as the integers 0 / 1 taken from a sign bit, each used once: a comparison whose result is both selected on and added up comes back from the
-        // compiler as a lane mask, a vector select and a read back into a scalar register — 30 cycles.)
-        #define KFL_EVENT(g_, g2_, k_, cg_) do { const int e_g = (g_), e_g2 = (g2_), e_k = (k_), e_cg = (cg_); \
-            cnt = kw::writelane(cnt, e_cg - e_k, (e_g - 1) & 63); \
-            const uint32_t e_in = e_g2 >= 1 ? 1u << ((e_g2 - 1) & 31) : 0u, e_out = (uint32_t)(e_cg - e_k - 1) >> 31;  /* bit g2 - 1 if g2 >= 1: the target level gains nodes | cg == k: the source level is emptied */ \
-            cnt = kw::writelane(cnt, kw::bcast(cnt, (e_g2 - 1) & 63) + e_k, (e_g2 - 1) & 63); \
-            nz = (nz & ~(e_out << ((e_g - 1) & 31))) | e_in; } while (0)
+        // k nodes leave level g, which holds cg >= k, for level g2 (0: none): two lanes of the counts are written, two bits of the non-empty mask change (bit g goes when the level
+        // is emptied, bit g2 comes: one scalar instruction each) — all of it on the scalar unit.  Nodes that leave for no level are counted in lane 0, whose bit is always set; a
+        // step without a level (g = 0, k = 0, g2 <= 0) adds nothing to any lane, and the gang it belongs to is rolled back.  (Bit 31 of the mask is never set: "clear nothing".)
+        #define KFL_EVENT(g_, g2_, k_, cg_) do { const int e_g = (g_), e_g2 = (g2_) > 0 ? (g2_) : 0, e_k = (k_), e_cg = (cg_); \
+            const int e_t = kw::bcast(cnt, e_g2 & 63); \
+            cnt = kw::writelane(cnt, e_cg - e_k, e_g & 63); \
+            cnt = kw::writelane(cnt, e_t + e_k, e_g2 & 63);  /* (read before the source's lane is written: g2 = g only without a level, where k = 0) */ \
+            nz = kw::bit_set(kw::bit_clear(nz, e_cg == e_k ? e_g : 31), e_g2); } while (0)
         // one step of a gang of ONE class, whole nodes: the lowest non-empty level g >= q holds r = g / q of its tasks per node; the first k nodes of it take r tasks each and move to
         // level g mod q, a remainder of fewer than r tasks goes to one node, which then stays at level g − rem·q.  No level: the step moves nothing and the gang has failed (it writes
         // a slot that stays unpublished: whatever its fields hold).
         // Spread: g is the highest non-empty level (the highest set bit of nz; `ok` says g >= q), r = 1: the first k = min(rest of the gang, nodes of the level) nodes take one task
         // each and move to g − q — no quotient table, no division.
         #define KFL_STEP(S, EMIT) \
-            const uint32_t lv##S = nz >> (qc - 1); \
+            const uint32_t lv##S = nz >> qc; \
             ok = kw::nonzero01(lv##S);  /* a level >= q holds a node — as a number, not as a comparison (kai_simt.hpp) */ \
-            const int g##S = lv##S ? (SP ? 32 - __builtin_clz(nz) : qc + __builtin_ctz(lv##S)) : 0, gm1##S = g##S - 1; \
+            const int g##S = lv##S ? (SP ? 31 - __builtin_clz(nz) : qc + __builtin_ctz(lv##S)) : 0; \
             int r##S = SP ? 1 : (int)((tq >> ((4 * g##S - 4) & 31)) & 15u); r##S = r##S > 1 ? r##S : 1;  /* kfl_quot(tq, g), at least 1 (no level: whatever, nothing moves) */ \
             const int rem##S = nt - placed; \
             const int kq##S = SP ? rem##S : (int)(((uint32_t)rem##S * (uint32_t)kw::bcast(invq, r##S - 1)) >> 15);  /* = kfl_div(rem, r): whole nodes the rest of the gang fills (0: a remainder of fewer than r tasks, on one node) */ \
-            const int cg##S = kw::bcast(cnt, gm1##S & 63); \
+            const int cg##S = kw::bcast(cnt, g##S & 63); \
             int k##S = kq##S < cg##S ? kq##S : cg##S; k##S = (k##S > 1 ? k##S : 1) * ok;  /* min(kq, nodes of the level), at least the one node; no level: nothing moves */ \
             const int per##S = r##S < rem##S ? r##S : rem##S, g2##S = g##S - per##S * qc; \
             EMIT(g##S, g2##S, k##S, per##S); \
@@ -184,8 +188,26 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         #define KFL_EMIT_RING(g_, g2_, k_, per_) KFL_EMIT(g_, g2_, k_, per_, first + placed)
         // a command's lower word without its job's index, held in lane jj of a register until the run is flushed (a gang that fails holds whatever: it is never stored)
         #define KFL_LOW(g_, g2_, k_, per_) (int)((uint32_t)(g_) | ((uint32_t)(g2_) << 4) | ((uint32_t)(per_) << 8) | ((uint32_t)(k_) << 12))
-        #define KFL_HOLD0(g_, g2_, k_, per_) c0 = kw::writelane(c0, KFL_LOW(g_, g2_, k_, per_), jj)
         #define KFL_HOLD1(g_, g2_, k_, per_) c1 = kw::writelane(c1, KFL_LOW(g_, g2_, k_, per_), jj)
+        // THE DECISION TABLE: lane j holds the first step of job j under the mask nz_tab, as one word — all that the step is but the level's population: bits 0-11 the command's
+        // lower word as it stands (g, g2, per; g = 0: no level >= q holds a node), bits 23-27 kq = the nodes the gang wants of the level (at least 1; the command's k = min(kq,
+        // nodes of the level) goes to bits 12-22, which the word leaves empty), bit 28: kq nodes are NOT all of the gang (so bits 23-28 as one number equal k iff one step places
+        // it), bit 29: a level was found, bit 30: which is not what the plan predicted.  Built by all lanes at once from the uniform mask and the lane's own job (short gangs
+        // only: the other lanes hold whatever), with kfl_div as plain per-lane arithmetic; exact for the mask it was built for, and rebuilt before the next gang reads its word
+        // whenever the mask differs (nz_tab == nz is the run's invariant).  mism: the jobs whose word has bit 30 set.
+        #define KFL_TABLE() do { \
+            const int t_q = s.q >= 1 ? s.q : 1, t_nt = s.nt; \
+            const uint32_t t_lv = nz >> t_q; \
+            const int t_g = SP ? 31 - __builtin_clz(nz) : t_q + __builtin_ctz(t_lv | 0x80000000u); \
+            int t_r = SP ? 1 : (int)((my_tq >> ((4 * t_g - 4) & 31)) & 15u); t_r = t_r > 1 ? t_r : 1; \
+            const int t_kq = SP ? t_nt : kfl_div(t_nt, t_r), t_kq1 = t_kq > 1 ? t_kq : 1; \
+            const int t_per = t_r < t_nt ? t_r : t_nt, t_g2 = t_g - t_per * t_q; \
+            const uint32_t t_p = s.flag == BF_OK ? 1u : 0u; \
+            const uint32_t t_w = (uint32_t)t_g | ((uint32_t)t_g2 << 4) | ((uint32_t)t_per << 8) | ((uint32_t)t_kq1 << 23) | (t_kq1 * t_per < t_nt ? 1u << 28 : 0u) | (1u << 29) | ((t_p ^ 1u) << 30); \
+            dw = t_lv ? t_w : t_p << 30; nz_tab = nz; mism = kw::ballot(((dw >> 30) & 1u) != 0); } while (0)
+        // of the jobs h, the ones up to the first whose word says "ends differently from its prediction" stay in h (that job is the round's last unless a second step or a new
+        // table says otherwise), the ones behind it wait in `held`: the loop tests nothing per gang for it
+        #define KFL_CUT(h) do { const uint64_t c_m = (h) & mism, c_keep = c_m ? ((c_m & (0 - c_m)) << 1) - 1 : ~0ull; held = (h) & ~c_keep; (h) &= c_keep; } while (0)
         // the end of a gang that went the long way: its outcome bit, what it placed before it failed (a stretch's decisions and rollbacks are summed up at its end: every task of a
         // committed gang is a decision, a gang that found no node for its next task booked the ones it placed and that one), Statement.Rollback (nothing was published: the counts, the
         // mask and the ring position), and whether it ended as predicted
@@ -193,10 +215,11 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
             okm |= (uint64_t)(uint32_t)(1 - fail) << jj; failm |= (uint64_t)(uint32_t)fail << jj; \
             extra += placed & (0 - fail); \
             cnt = fail ? cnt_s : cnt; nz = fail ? nz_s : nz; wp = fail ? wp_s : wp; \
-            const int mism = (int)((uint32_t)(flag - 1) >> 31) ^ fail ^ 1;  /* (flag == BF_OK) != ok — the job ended differently from its prediction: it is the round's last */ \
-            mismatch |= mism; last_jj = jj
+            const int g_mis = (int)((uint32_t)(flag - 1) >> 31) ^ fail ^ 1;  /* (flag == BF_OK) != ok — the job ended differently from its prediction: it is the round's last */ \
+            mismatch |= g_mis; last_jj = jj
         // the 64 jobs of a stretch: one per lane; the NEXT stretch's loads are issued before this stretch is walked
         int nx_flag = 0, nx_first = 0, nx_nt = 0, nx_ucls = 0;
+        uint32_t dw = 0, nz_tab = ~0u; uint64_t mism = 0;  // the decision table, the mask it was built for (~0: none — a new stretch's jobs) and its mispredicted jobs
         if (V > rp.start) { const int gc = rp.start + lane < V ? rp.start + lane : V - 1; nx_flag = b.g_flag[gc]; nx_first = b.g_first[gc]; nx_nt = b.g_nt[gc]; nx_ucls = b.g_ucls[gc]; }
         for (int base = rp.start; base < V && !mismatch; base += 64) {
             const int gi = base + lane;
@@ -206,14 +229,15 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
             { const int gc = gi + 64 < V ? gi + 64 : V - 1; nx_flag = b.g_flag[gc]; nx_first = b.g_first[gc]; nx_nt = b.g_nt[gc]; nx_ucls = b.g_ucls[gc]; }
             const int jn = V - base < 64 ? V - base : 64;
             int capq = 0;  // lane q − 1: the tasks that ask for q devices the levels hold at the stretch's start
-            for (int g = 1; g <= v.LV; g++) capq += kfl_quot(tab, g) * kw::bcast(cnt, g - 1);
+            for (int g = 1; g <= v.LV; g++) capq += kfl_quot(tab, g) * kw::bcast(cnt, g);
             kfl_classify(s, my_ucls, qk, capq);
             // a job's parameters in one word: flag (2 bits), devices (5 bits), tasks (up to KB_PLACED_MAX: 11 bits), bit 19: predicted to fit, bit 18: the long way (several classes, more tasks than the
             // stretch's reservation in the ring covers, or none at all: the short way takes its first step without asking)
             const int my_pack = s.flag | (s.q << 2) | (s.nt << 7) | ((s.q == 0 || s.nt > KFL_SHORT || s.nt < 1) ? 1 << 18 : 0) | (s.flag == BF_OK ? 1 << 19 : 0);
             const uint32_t my_tq = kw::shfl(tab, s.q >= 1 ? s.q - 1 : 63);  // the quotients g / q of the job's request
             uint64_t longm = kw::ballot(((my_pack >> 18) & 1) != 0);
-            uint64_t todo = s.todo, okm = 0, failm = 0, okw = 0;  // okm / failm: jobs of this stretch that committed / that were walked and found no room; okw: the walked jobs of its runs that found room
+            nz_tab = ~0u;
+            uint64_t todo = s.todo, okm = 0, failm = 0;  // okm / failm: jobs of this stretch that committed / that were walked and found no room
             int n_out = jn, last_jj = 0, extra = 0;  // extra: tasks the failed gangs had placed before they failed
             attempted += jn; n_done = base + jn;
             KFL_ROOM(1);  // room for the stretch's marker (a run asks for the room of its commands when it is flushed, a long gang before it starts: no check per gang)
@@ -225,8 +249,8 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
             KFL_T(0);
             // (a conditional branch costs this wavefront 22 - 31 cycles whether it is taken or not, a scalar instruction 5 - 6, a dependent vector instruction 7, a vector compare that
             // feeds the scalar unit 30 — tools/micro/issue_rate.hip.  So the usual gang — one class, 1 .. KFL_SHORT tasks — runs straight through: the short gangs in front of the next
-            // long one, a RUN, are walked by a loop that holds nothing else, its first step without a test, one rarely taken branch for a second step, and ONE test at its end for
-            // "more to walk, predicted right".  Everything but the counts lives in scalar registers.
+            // long one, a RUN, are walked by a loop that holds nothing else: the first step read from the decision table, ONE rarely taken branch for "a second step or a new table", and
+            // the loop's own test (the run is cut in front of the first job the table says is predicted wrong).  Everything but the counts and the table lives in scalar registers.
             // A run stores nothing: the lower word of a gang's command goes into lane jj of c0, that of a second step into c1, and the run is FLUSHED at its end — every lane forms
             // the upper words and the job bits of its own gang's commands, a prefix sum gives it their place in the ring, head is published once.  The ring receives the words in
             // the jobs' order, as if every gang had written its own.  A first step that finds no level moves nothing (k = 0), so only a gang that takes a second step needs the
@@ -237,33 +261,52 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                 uint64_t hot = todo & below;
                 todo &= ~below;
                 if (hot) {
-                    const uint64_t run0 = hot; uint64_t twor = 0, rest = 0;  // the run's jobs / the ones among them that committed with two commands / the ones a third step left unwalked
-                    int c0 = 0, c1 = 0, jj, pred, ok;
+                    const uint64_t run0 = hot; uint64_t twor = 0, rest = 0, fail2 = 0, held;  // the run's jobs / the ones among them that committed with two commands / the ones a third step left unwalked / the ones a second step rolled back / the ones behind the first job the table says ends differently from its prediction
+                    // (held != 0 only while the last job of `hot` is one the table says is predicted wrong: KFL_CUT is the only place that fills it, and every path that changes the
+                    // table, or that job's outcome, either empties it or cuts again.  The jobs of a run are hot | held | the ones walked | rest at any time.)
+                    int c0 = 0, c1 = 0, jj; uint32_t w;
+                    if (nz != nz_tab) { KFL_TABLE(); }  // (a new stretch, or a long gang changed the mask)
+                    KFL_CUT(hot);
                     do {
-                        jj = __builtin_ctzll(hot); hot &= hot - 1;
-                        const int pack = kw::bcast(my_pack, jj);
-                        const uint32_t tq = kw::bcast(my_tq, jj);
-                        const int qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff;
-                        pred = (pack >> 19) & 1;  // flag == BF_OK
+                        jj = __builtin_ctzll(hot); hot = kw::bit_clear(hot, jj);
+                        w = kw::bcast(dw, jj);
                         KFL_T(1);
-                        const uint32_t nz_s = nz;
-                        int placed = 0;
-                        KFL_STEP(A, KFL_HOLD0);
-                        if (__builtin_expect(placed < nt * ok, 0)) {
-                            // the counts in front of the gang: the first step taken back
-                            int cnt_s = kw::writelane(cnt, kw::bcast(cnt, (g2A - 1) & 63) - kA, (g2A - 1) & 63); cnt_s = kw::writelane(cnt_s, cgA, gm1A & 63);
-                            KFL_STEP(B, KFL_HOLD1);
-                            if (!ok) { cnt = cnt_s; nz = nz_s; extra += placed; }  // Statement.Rollback: it booked the tasks it placed and the one that found no node
-                            else if (placed < nt) {  // a third step: not in lanes — the run ends in front of this gang, which then goes the long way (no outcome here: `ok` is set to what was predicted and taken out of okw below)
-                                cnt = cnt_s; nz = nz_s; longm |= 1ull << jj; rest = hot | (1ull << jj); hot = 0; ok = pred;
-                            } else twor |= 1ull << jj;
+                        // the gang's first step as the table has it: k = min(kq, nodes of the level) nodes of level g move to g2 (no level: g = g2 = kq = 0, nothing moves)
+                        const int g = w & 15, g2 = (w >> 4) & 15;
+                        const int cg = kw::bcast(cnt, g), t2 = kw::bcast(cnt, g2);
+                        const int kq = (w >> 23) & 31, k = kq < cg ? kq : cg;
+                        c0 = kw::writelane(c0, (int)(w | ((uint32_t)k << 12)), jj);
+                        cnt = kw::writelane(cnt, cg - k, g);
+                        cnt = kw::writelane(cnt, t2 + k, g2);
+                        nz = kw::bit_set(kw::bit_clear(nz, cg == k ? g : 31), g2);
+                        // out of line, one test for both: the step did not place the whole gang (k is not the kq of a word that says "kq nodes are all of it") | the mask is no longer the table's
+                        // (as ONE number the compiler knows nothing about: left to itself it keeps the two comparisons apart, as three lane masks and their conjunction)
+                        if (__builtin_expect(kw::opaque((uint32_t)(k ^ (int)((w >> 23) & 63)) | (nz ^ nz_tab)) != 0, 0)) {
+                            if (k != (int)((w >> 23) & 63)) {
+                                const int pack = kw::bcast(my_pack, jj);
+                                const uint32_t tq = kw::bcast(my_tq, jj);
+                                const int qc = (pack >> 2) & 31, nt = (pack >> 7) & 0x7ff, pred = (pack >> 19) & 1;
+                                const uint32_t nz_s = nz_tab;  // (the mask in front of the gang: the table was built for it)
+                                int placed = k * (int)((w >> 8) & 15), ok;
+                                // the counts in front of the gang: the first step taken back
+                                int cnt_s = kw::writelane(cnt, t2, g2); cnt_s = kw::writelane(cnt_s, cg, g);
+                                KFL_STEP(B, KFL_HOLD1);
+                                if (!ok) { cnt = cnt_s; nz = nz_s; extra += placed; fail2 |= 1ull << jj; }  // Statement.Rollback: it booked the tasks it placed and the one that found no node
+                                else if (placed < nt) {  // a third step: not in lanes — the run ends in front of this gang, which then goes the long way (no outcome here: it counts as predicted right and is taken out of `walked` below)
+                                    cnt = cnt_s; nz = nz_s; longm |= 1ull << jj; rest = hot | held | (1ull << jj); hot = 0; held = 0; ok = pred;
+                                } else twor |= 1ull << jj;
+                                w = (w & ~(1u << 30)) | ((uint32_t)(pred ^ ok) << 30);
+                            }
+                            if ((w >> 30) & 1) { hot = 0; held = 0; }  // a job that ends differently from its prediction is the round's last: nothing behind it is walked
+                            else {
+                                if (nz != nz_tab) { KFL_TABLE(); }
+                                hot |= held; KFL_CUT(hot);
+                            }
                         }
                         KFL_T(2);
-                        okw |= (uint64_t)(uint32_t)ok << jj;
-                        hot = kw::opaque(pred == ok ? hot : (uint64_t)0);  // a job that ends differently from its prediction is the round's last: nothing behind it is walked
-                        KFL_T(3);
                     } while (hot);
-                    mismatch |= pred ^ ok;
+                    mismatch |= (int)((w >> 30) & 1);
+                    const uint64_t okw = kw::ballot(((c0 >> 29) & 1) != 0) & ~fail2;  // the walked jobs that found room: the first step's word says so, unless a second step was rolled back
                     const uint64_t walked = run0 & ((2ull << jj) - 1) & ~rest, okr = walked & okw;  // (the jobs of the run up to the last one walked)
                     failm |= walked & ~okw; hot |= rest;
                     // the flush: lane j stores the commands of job j
@@ -275,7 +318,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                         KFL_ROOM(n_run);
                         const int pos = wp + incl - n_my;
                         const uint32_t jb = (uint32_t)lane << KFL_JOB_SHIFT;
-                        if (n_my >= 1) L.ring[pos & (KFL_RING - 1)] = (uint64_t)((uint32_t)c0 | jb) | ((uint64_t)(uint32_t)s.first << 32);
+                        if (n_my >= 1) L.ring[pos & (KFL_RING - 1)] = (uint64_t)(((uint32_t)c0 & 0x7fffffu) | jb) | ((uint64_t)(uint32_t)s.first << 32);
                         if (n_my >= 2) L.ring[(pos + 1) & (KFL_RING - 1)] = (uint64_t)((uint32_t)c1 | jb) | ((uint64_t)(uint32_t)(s.first + ((c0 >> 12) & 0x7ff) * ((c0 >> 8) & 15)) << 32);
                         wp += n_run;
                         kw::lds_store_rel(&L.head, wp); pub = wp;
@@ -304,7 +347,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                                 const int g = q1 <= 31 ? KFL_LEVEL_FOR(q1) : 0;
                                 if (!g) { ok = 0; break; }
                                 KFL_EMIT(g, g - q1, 1, 1, first + placed);
-                                KFL_EVENT(g, g - q1, 1, kw::bcast(cnt, g - 1));
+                                KFL_EVENT(g, g - q1, 1, kw::bcast(cnt, g));
                                 placed++;
                             }
                         }
@@ -314,7 +357,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                     KFL_GANG_END();
                     if (wp - pub >= 64) { kw::lds_store_rel(&L.head, wp); pub = wp; }
                     KFL_T(3);
-                    if (mism) break;
+                    if (g_mis) break;
                 }
             }
             if (mismatch) { n_done = base + last_jj + 1; n_out = last_jj + 1; attempted -= jn - n_out; }
@@ -339,13 +382,14 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         #undef KFL_STEP
         #undef KFL_EMIT_RING
         #undef KFL_LOW
-        #undef KFL_HOLD0
+        #undef KFL_TABLE
+        #undef KFL_CUT
         #undef KFL_HOLD1
         #undef KFL_GANG_END
         if (lane == 0) L.fin = n_done;
         kw::lds_store_rel(&L.head, wp);
         kw::lds_store_rel(&L.done, 1);
-        const uint64_t dead = kw::ballot(act && (qk > 32 || (nz >> (qk - 1)) == 0));
+        const uint64_t dead = kw::ballot(act && (qk > 32 || ((nz >> 1) >> (qk - 1)) == 0));
         if (lane == 0) {
             FillStatus s; s.n_done = n_done; s.mismatch = mismatch; s.all_dead = (C > 0 && dead == (C >= 64 ? ~0ull : ((1ull << C) - 1))) ? 1 : 0; s.planned = V; s.floor_stop = 0; s.pad = 0;
             s.decisions = decisions; s.attempted = attempted; s.committed = committed; s.rollbacks = rollbacks; s.ops = ops; s.dead_mask = dead;  // (decisions: the bookkeeper's part is added below)

@@ -52,8 +52,14 @@ KW_DEV int rank_below(uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint3
 // v != 0 as the number 0 / 1 for a uniform v (the same in every lane), in ONE scalar instruction the compiler knows nothing about: a truth value that is selected on, multiplied with and
 // added up comes back from the compiler as a lane mask, a vector select and a read back into a scalar register (30 cycles on a chain of dependent instructions)
 KW_DEV int nonzero01(uint32_t v) { int r; asm("s_min_u32 %0, %1, 1" : "=s"(r) : "s"(v) : "scc"); return r; }
+// the uniform v with bit `bit` (uniform; its low 5 / 6 bits count) cleared / set, in ONE scalar instruction (s_bitset0 / s_bitset1): the compiler builds the mask with a shift
+// and combines it with a second instruction, and for "the lowest set bit goes" (v & (v − 1)) on 64 bits it takes an add, an add with carry and an and
+KW_DEV uint32_t bit_clear(uint32_t v, int bit) { asm("s_bitset0_b32 %0, %1" : "+s"(v) : "s"(bit)); return v; }
+KW_DEV uint32_t bit_set(uint32_t v, int bit) { asm("s_bitset1_b32 %0, %1" : "+s"(v) : "s"(bit)); return v; }
+KW_DEV uint64_t bit_clear(uint64_t v, int bit) { asm("s_bitset0_b64 %0, %1" : "+s"(v) : "s"(bit)); return v; }
 // a uniform 64-bit value the compiler knows nothing about from here on
 KW_DEV uint64_t opaque(uint64_t v) { v = uni(v); asm("" : "+s"(v)); return v; }
+KW_DEV uint32_t opaque(uint32_t v) { v = uni(v); asm("" : "+s"(v)); return v; }
 // a hint to the SIMD's arbiter: 0 (default) .. 3, the wavefront with the higher priority issues first (s_setprio)
 template <int P> KW_DEV void set_prio() { __builtin_amdgcn_s_setprio(P); }
 KW_DEV int atomic_add(int32_t* p, int v) { return atomicAdd(p, v); }
@@ -243,7 +249,11 @@ inline int writelane(int old, int v, int dst) { return lane() == dst ? v : old; 
 inline uint64_t writelane(uint64_t old, uint64_t v, int dst) { return lane() == dst ? v : old; }
 inline int rank_below(uint64_t m) { return __builtin_popcountll(m & ((1ull << lane()) - 1)); }
 inline int nonzero01(uint32_t v) { return v ? 1 : 0; }
+inline uint32_t bit_clear(uint32_t v, int bit) { return v & ~(1u << (bit & 31)); }
+inline uint32_t bit_set(uint32_t v, int bit) { return v | (1u << (bit & 31)); }
+inline uint64_t bit_clear(uint64_t v, int bit) { return v & ~(1ull << (bit & 63)); }
 inline uint64_t opaque(uint64_t v) { return v; }
+inline uint32_t opaque(uint32_t v) { return v; }
 template <int P> inline void set_prio() {}
 inline int atomic_add(int32_t* p, int v) { int o = *p; *p = o + v; return o; }
 inline int atomic_min(int32_t* p, int v) { int o = *p; if (v < o) *p = v; return o; }
