@@ -154,7 +154,7 @@ typedef struct kai_config {
                                              class needs a node bitmap of its own; every other session runs the general fill kernel.  Same results either way. */
     int32_t reserved[7];
     /* minruntime plugin (plugins/minruntime/minruntime.go:40-100): "now" of the cycle, plugin-argument defaults, reclaim resolve method */
-    int64_t now_ns;
+    int64_t now_ns;                       /* the FIRST cycle's clock: kai_core_set_now / kai_session_rows.now_ns move it on the same handle */
     int64_t default_preempt_min_runtime_ns;
     int64_t default_reclaim_min_runtime_ns;
     int32_t reclaim_resolve_method;       /* 0 = lca (default), 1 = queue */
@@ -402,8 +402,9 @@ int kai_session_reset(kai_core* core);
  *  Every refusal is decided before the first write and leaves the session exactly as it was (still open, same snapshot, same state); only a HIP failure after
  *  the writes began closes it, as a failed open does.  The host work is proportional to the delta (plus, in a session with shared-GPU requests, one pass over
  *  the nodes' lists of active pods); the session math is re-derived on the device as kai_session_reset does.
- *  Anything the delta cannot express needs a full open: pods, jobs, pod-sets, queues or nodes added or removed; requests, classes, class_fit, topologies,
- *  queue quotas or the config changed. */
+ *  Anything the delta and the rows below cannot express needs a full open: pods, jobs, pod-sets, queues or nodes added or removed; job_priority,
+ *  job_preemptible, job_queue; queue_parent, queue_created_ns, queue_uid_rank; requests, classes, class_fit, topologies; any kai_config field other
+ *  than now_ns. */
 #define KAI_DELTA_VERSION 1u
 typedef struct kai_session_delta {
     uint32_t version;                /* KAI_DELTA_VERSION */
@@ -418,6 +419,45 @@ typedef struct kai_session_delta {
     const double* node_allocatable;  /* [R][n_nodes] new status.allocatable; NULL = unchanged */
 } kai_session_delta;
 int kai_session_update(kai_core* core, const kai_session_delta* delta);
+
+/* The cycle's clock (kai_config.now_ns; only the minruntime filters read it).  It takes effect at once on an open session, without any re-derivation, and is
+ * what every later kai_session_open / kai_session_reset / kai_session_update of this handle uses.  Works without an open session. */
+int kai_core_set_now(kai_core* core, int64_t now_ns);
+
+/* What changes between two cycles beside the pods and nodes, none of it structural: the cycle's clock, queue rows (quota, limit, over-quota weight, the
+ * normalised historical usage, priority, the two min-runtime settings) and the jobs' last start times.  Applied together with a pod / node delta by ONE pass:
+ * one staging copy, one scatter, one re-derivation.
+ *
+ * Contract: the one of kai_session_update, extended.  Let S, cfg be the snapshot and the configuration of the last open or update and S', cfg' be them with
+ * the delta and the rows applied.  After KAI_OK the handle is indistinguishable from a fresh handle created with cfg' that has run kai_session_open(S'):
+ * read-backs bit for bit, everything every later action returns, and kai_session_reset returns to S'.
+ *  - KAI_ERR_INVALID_ARG: what kai_session_update refuses in the delta; in the rows a wrong version, unknown `fields` bits, a negative count, a NULL index
+ *    array with a count above 0, a queue or job index out of range or listed twice;
+ *  - KAI_ERR_STATE: no open session;  KAI_ERR_UNSUPPORTED: a handle of a sharded group, and what kai_session_update refuses.
+ *  Every refusal is decided before the first write, for both parts together: a valid delta with invalid rows writes nothing and leaves the session open on S.
+ *  An optional array that was NULL at the open (queue_usage, job_last_start_ns, the two min-runtime arrays) exists in S' once a call carries it for at least
+ *  one row, with the value an absent array stands for (0, 0, -1, -1) in every row the call does not name.
+ *  delta and rows may each be NULL; kai_session_update(core, d) == kai_session_update_rows(core, d, NULL). */
+#define KAI_ROWS_VERSION 1u
+#define KAI_ROWS_HAS_NOW 0x1u
+typedef struct kai_session_rows {
+    uint32_t version;   /* KAI_ROWS_VERSION */
+    uint32_t fields;    /* KAI_ROWS_HAS_NOW: now_ns is set */
+    int64_t  now_ns;
+    int32_t  n_queues;  /* queues whose rows changed */
+    const int32_t* queue;                        /* [n_queues] queue index */
+    const double*  queue_deserved;               /* [3][n_queues], units of the snapshot's; NULL = unchanged (likewise below) */
+    const double*  queue_limit;                  /* [3][n_queues] */
+    const double*  queue_oqw;                    /* [3][n_queues] */
+    const double*  queue_usage;                  /* [3][n_queues] */
+    const int32_t* queue_priority;               /* [n_queues] */
+    const int64_t* queue_preempt_min_runtime_ns; /* [n_queues], -1 = not set on that queue */
+    const int64_t* queue_reclaim_min_runtime_ns; /* [n_queues] */
+    int32_t  n_jobs;    /* jobs whose rows changed */
+    const int32_t* job;                          /* [n_jobs] job index */
+    const int64_t* job_last_start_ns;            /* [n_jobs]; NULL = unchanged */
+} kai_session_rows;
+int kai_session_update_rows(kai_core* core, const kai_session_delta* delta, const kai_session_rows* rows);
 
 /* replaces: ssn.QueueFairShare / QueueAllocatedResources / QueueDeservedResources
  * (plugins/proportion/proportion.go:508-521) */

@@ -40,7 +40,7 @@ PLUGIN_SUBGROUPORDER, PLUGIN_TASKORDER, PLUGIN_NOMINATEDNODE, PLUGIN_NODEPLACEME
 PLUGIN_ALL = 0x3FFF  # the default tier list (conf_util/scheduler_conf_util.go:36-61): everything except gpuspread
 
 STATUS_TEXT = {0: "ok", -1: "invalid argument", -2: "no HIP device", -3: "HIP runtime error", -4: "output capacity",
-               -5: "unsupported snapshot feature", -6: "call order", -7: "device engine fault", -8: "multi-GPU exchange"}
+               -5: "unsupported snapshot feature", -6: "call order", -7: "device engine fault", -8: "multi-GPU exchange", -9: "out of host memory"}
 
 
 class KaiConfig(C.Structure):
@@ -140,6 +140,61 @@ def apply_delta(snap: "Snapshot", pods, status, node, gpu_group=None, nodes=None
                    queue_names=snap.queue_names, podset_names=snap.podset_names)
     out.finalize()
     return out
+
+
+ROWS_VERSION = 1  # KAI_ROWS_VERSION
+ROWS_HAS_NOW = 0x1
+
+
+class KaiSessionRows(C.Structure):
+    """kai_session_rows (include/kai_core.h): the cycle's clock, queue rows and job start times applied by kai_session_update_rows."""
+    _fields_ = [("version", C.c_uint32), ("fields", C.c_uint32), ("now_ns", C.c_int64), ("n_queues", C.c_int32), ("queue", C.POINTER(C.c_int32)),
+                ("queue_deserved", C.POINTER(C.c_double)), ("queue_limit", C.POINTER(C.c_double)), ("queue_oqw", C.POINTER(C.c_double)),
+                ("queue_usage", C.POINTER(C.c_double)), ("queue_priority", C.POINTER(C.c_int32)), ("queue_preempt_min_runtime_ns", C.POINTER(C.c_int64)),
+                ("queue_reclaim_min_runtime_ns", C.POINTER(C.c_int64)), ("n_jobs", C.c_int32), ("job", C.POINTER(C.c_int32)),
+                ("job_last_start_ns", C.POINTER(C.c_int64))]
+
+
+def copy_config(cfg: KaiConfig) -> KaiConfig:
+    out = KaiConfig()
+    C.memmove(C.byref(out), C.byref(cfg), C.sizeof(KaiConfig))
+    return out
+
+
+def apply_rows(snap: "Snapshot", cfg: KaiConfig, now_ns=None, queues=None, queue_deserved=None, queue_limit=None, queue_oqw=None, queue_usage=None,
+               queue_priority=None, queue_preempt_min_runtime_ns=None, queue_reclaim_min_runtime_ns=None, jobs=None, job_last_start_ns=None):
+    """(S', cfg') = (S, cfg) with a kai_session_rows applied: a new Snapshot (the arrays the rows touch are copied, the others shared) and a new KaiConfig that
+    kai_core_create / kai_session_open accept.  The four queue quantities are [3][len(queues)], as in the C struct.  An optional array the snapshot lacks and the
+    rows carry for at least one row is created with the value an absent array stands for (0 for queue_usage and job_last_start_ns, -1 for the min-runtimes)."""
+    a = dict(snap.arrays)
+    cfg2 = copy_config(cfg)
+    if now_ns is not None:
+        cfg2.now_ns = int(now_ns)
+    Q, J = snap.n_queues, snap.n_jobs
+
+    def put(name, idx, val, shape, dt, absent):
+        if val is None or not len(idx):
+            return
+        arr = a[name].copy() if name in a else np.full(shape, absent, dt)
+        if arr.ndim == 2:
+            arr[:, idx] = np.asarray(val, dt).reshape(3, len(idx))
+        else:
+            arr[idx] = np.asarray(val, dt)
+        a[name] = arr
+    qi = np.asarray([] if queues is None else queues, np.int64)
+    ji = np.asarray([] if jobs is None else jobs, np.int64)
+    put("queue_deserved", qi, queue_deserved, (3, Q), np.float64, 0.0)
+    put("queue_limit", qi, queue_limit, (3, Q), np.float64, 0.0)
+    put("queue_oqw", qi, queue_oqw, (3, Q), np.float64, 0.0)
+    put("queue_usage", qi, queue_usage, (3, Q), np.float64, 0.0)
+    put("queue_priority", qi, queue_priority, (Q,), np.int32, 0)
+    put("queue_preempt_min_runtime_ns", qi, queue_preempt_min_runtime_ns, (Q,), np.int64, -1)
+    put("queue_reclaim_min_runtime_ns", qi, queue_reclaim_min_runtime_ns, (Q,), np.int64, -1)
+    put("job_last_start_ns", ji, job_last_start_ns, (J,), np.int64, 0)
+    out = Snapshot(n_res=snap.n_res, arrays=a, node_names=snap.node_names, pod_names=snap.pod_names, job_names=snap.job_names,
+                   queue_names=snap.queue_names, podset_names=snap.podset_names)
+    out.finalize()
+    return out, cfg2
 
 
 def next_cycle_delta(snap: "Snapshot", ops, rng, succeeded_frac=0.01) -> dict:

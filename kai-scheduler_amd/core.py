@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
 EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node",
-           "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_close", "kai_last_error", "kai_version"]
+           "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
 _OP_DTYPE = np.dtype([("seq", "<i8"), ("kind", "<i4"), ("pod", "<i4"), ("node", "<i4"), ("job", "<i4"), ("stmt", "<i4"), ("pad", "<i4")])  # kai_op (include/kai_core.h)
@@ -43,6 +43,32 @@ def delta_struct(pods, status, node, gpu_group=None, nodes=None, node_flags=None
     d.n_nodes = 0 if keep[4] is None else len(keep[4])
     d.node, d.node_flags, d.node_allocatable = ptr(keep[4], C.c_int32), ptr(keep[5], C.c_uint32), ptr(keep[6], C.c_double)
     return d, keep
+
+
+def rows_struct(now_ns=None, queues=None, queue_deserved=None, queue_limit=None, queue_oqw=None, queue_usage=None, queue_priority=None,
+                queue_preempt_min_runtime_ns=None, queue_reclaim_min_runtime_ns=None, jobs=None, job_last_start_ns=None, version=abi.ROWS_VERSION, fields=None):
+    """A kai_session_rows and the numpy arrays it points into (keep them alive while the struct is in use); None = a NULL array.
+    The four queue quantities are [3][len(queues)]."""
+    def arr(x, dt):
+        return None if x is None else np.ascontiguousarray(x, dtype=dt)
+    def ptr(x, ct):
+        return None if x is None else x.ctypes.data_as(C.POINTER(ct))
+    q, j = arr(queues, np.int32), arr(jobs, np.int32)
+    f64 = [arr(x, np.float64) for x in (queue_deserved, queue_limit, queue_oqw, queue_usage)]
+    for x in f64:
+        assert x is None or x.size == 3 * (0 if q is None else len(q)), "a queue quantity is [3][len(queues)]"
+    prio, pmr, rmr, jls = arr(queue_priority, np.int32), arr(queue_preempt_min_runtime_ns, np.int64), arr(queue_reclaim_min_runtime_ns, np.int64), arr(job_last_start_ns, np.int64)
+    r = abi.KaiSessionRows()
+    r.version = version
+    r.fields = (abi.ROWS_HAS_NOW if now_ns is not None else 0) if fields is None else fields
+    r.now_ns = 0 if now_ns is None else int(now_ns)
+    r.n_queues = 0 if q is None else len(q)
+    r.queue = ptr(q, C.c_int32)
+    r.queue_deserved, r.queue_limit, r.queue_oqw, r.queue_usage = (ptr(x, C.c_double) for x in f64)
+    r.queue_priority, r.queue_preempt_min_runtime_ns, r.queue_reclaim_min_runtime_ns = ptr(prio, C.c_int32), ptr(pmr, C.c_int64), ptr(rmr, C.c_int64)
+    r.n_jobs = 0 if j is None else len(j)
+    r.job, r.job_last_start_ns = ptr(j, C.c_int32), ptr(jls, C.c_int64)
+    return r, [q, j, prio, pmr, rmr, jls] + f64
 
 
 class KaiError(RuntimeError):
@@ -92,6 +118,8 @@ def load_library(path: str = LIB_PATH):
     lib.kai_pod_gpu_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
     lib.kai_session_reset.argtypes = [C.c_void_p]
     lib.kai_session_update.argtypes = [C.c_void_p, C.POINTER(abi.KaiSessionDelta)]
+    lib.kai_session_update_rows.argtypes = [C.c_void_p, C.POINTER(abi.KaiSessionDelta), C.POINTER(abi.KaiSessionRows)]
+    lib.kai_core_set_now.argtypes = [C.c_void_p, C.c_int64]
     lib.kai_queue_shares.argtypes = [C.c_void_p, C.POINTER(abi.KaiQueueShare), C.c_int]
     lib.kai_action_execute.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64)]
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
@@ -204,6 +232,12 @@ class KaiCore:
         if rc != 0:
             raise KaiError(rc, self.lib.kai_last_error(self.handle).decode())
 
+    def set_now(self, now_ns: int):
+        """kai_core_set_now: the cycle's clock, at once on an open session and for every later open / reset / update of this handle."""
+        self._check(self.lib.kai_core_set_now(self.handle, int(now_ns)))
+        self.cfg = abi.copy_config(self.cfg)  # (the caller's structure stays as it was handed in)
+        self.cfg.now_ns = int(now_ns)
+
     def open_session(self, snap: abi.Snapshot) -> "Session":
         s = snap.as_struct()
         self._check(self.lib.kai_session_open(self.handle, C.byref(s)))
@@ -307,6 +341,20 @@ class Session:
         d, _keep = delta_struct(pods, status, node, gpu_group, nodes, node_flags, node_allocatable)
         self.core._check(self.core.lib.kai_session_update(self.core.handle, C.byref(d)))
         self.snap = abi.apply_delta(self.snap, pods, status, node, gpu_group, nodes, node_flags, node_allocatable)
+
+    def update_rows(self, delta_args=None, rows_args=None):
+        """kai_session_update_rows: a pod / node delta (keyword arguments of `update`, or None) and the rows (keyword arguments of rows_struct / abi.apply_rows, or
+        None) applied in one pass.  On success self.snap becomes S' and the core's config cfg'."""
+        d = keep = r = keep2 = None
+        if delta_args is not None:
+            d, keep = delta_struct(**delta_args)
+        if rows_args is not None:
+            r, keep2 = rows_struct(**rows_args)
+        self.core._check(self.core.lib.kai_session_update_rows(self.core.handle, None if d is None else C.byref(d), None if r is None else C.byref(r)))
+        if delta_args is not None:
+            self.snap = abi.apply_delta(self.snap, **delta_args)
+        if rows_args is not None:
+            self.snap, self.core.cfg = abi.apply_rows(self.snap, self.core.cfg, **rows_args)
 
     def close(self):
         self.core.lib.kai_session_close(self.core.handle)

@@ -965,20 +965,25 @@ int kai_session_reset(kai_core* core) {
 // and sent in one copy, k_delta_gather reads the snapshot's side of every changed pod (no write); (3) the open's refusals against S', on the host; (4) the counters the
 // open derives by walking the pods and nodes, adjusted old -> new, and the class table ranked again (host, proportional to the delta); (5) k_apply_delta scatters into
 // the baselines, the class labels are re-derived if the table changed, and the session math is re-derived on the device as kai_session_reset does.
+// kai_session_update_rows adds the rows (the clock, queue rows, job start times): checked with the delta in (1), staged behind it in the same buffer and sent by the same
+// copy in (2), HostPrep::shares and the clock set in (4), k_apply_rows beside k_apply_delta in (5) — one re-derivation for both parts.
 static constexpr int32_t KD_ACTIVE = KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING;
 
-static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote) {
+static int update_impl(kai_core* core, const kai_session_delta* dl, const kai_session_rows* rw, bool& wrote) {
     const bool prof = std::getenv("KAI_PROF") != nullptr;  // host clocks of the update (stderr), as kai_session_open reports its own
     const auto t0 = std::chrono::steady_clock::now();
     auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     int gpu_nodes_after = -1;
     KaiCtx& c = core->ctx; HostPrep& prep = core->prep; SharedPods& sp = core->sp;
     const int N = c.N, P = c.P, R = c.R, NP = dl->n_pods, NN = dl->n_nodes;
+    const int NQ = rw ? rw->n_queues : 0, NJ = rw ? rw->n_jobs : 0;
     HIP_TRY(core, hipSetDevice(core->device));
-    // ---- (2) staging: [pod | status | node | group | node | flags] int32, then [R][NN] doubles; the gather's output and counters behind it
+    // ---- (2) staging: [pod | status | node | group | node | flags] int32, then [R][NN] doubles, then the rows ([queue | priority | job] int32, then 8-byte values:
+    // deserved, limit, oqw, usage [3][NQ] each, the two min-runtimes [NQ] each, last start [NJ]); the gather's output and counters behind it
     auto up8 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int NNcap = NN + (core->legacy_on ? 2 * NP : 0);  // node entries: the delta's, and the nodes whose legacy-MIG bit a pod of the delta changes
-    const size_t o_i32 = 0, n_i32 = (size_t)4 * NP + 2 * NNcap, o_f64 = up8(n_i32 * 4), o_out = up8(o_f64 + (size_t)R * NNcap * 8), o_cnt = up8(o_out + (size_t)4 * NP * 4), total = o_cnt + 256;
+    const size_t o_i32 = 0, n_i32 = (size_t)4 * NP + 2 * NNcap, o_f64 = up8(n_i32 * 4), o_r32 = up8(o_f64 + (size_t)R * NNcap * 8), o_r64 = up8(o_r32 + ((size_t)2 * NQ + NJ) * 4),
+                 o_out = up8(o_r64 + ((size_t)14 * NQ + NJ) * 8), o_cnt = up8(o_out + (size_t)4 * NP * 4), total = o_cnt + 256;
     if (total > core->dl_pin_bytes) {
         if (core->dl_pin) (void)hipHostFree(core->dl_pin);
         core->dl_pin = nullptr; core->dl_pin_bytes = 0;
@@ -1007,6 +1012,21 @@ static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote)
         const int e = eng[(size_t)k]; hnode[k] = dl->node[k];
         hflags[k] = dl->node_flags ? ((dl->node_flags[k] & 0x0FFFFFFFu) | (prep.node_flags[(size_t)e] & 0xF0000000u)) : prep.node_flags[(size_t)e];  // the caller's bits masked as the open does, the library's own kept
         for (int r = 0; r < R; r++) h64[(size_t)r * NN + k] = node_row(k, r);
+    }
+    // the rows: an array the call leaves NULL takes no part (its slot in the buffer is sent as it is and never read)
+    RowsView rv{}; rv.n_queues = NQ; rv.n_jobs = NJ;
+    {   unsigned char* dv0 = core->dl_dev;
+        int32_t* r32 = reinterpret_cast<int32_t*>(core->dl_pin + o_r32); unsigned char* r64 = core->dl_pin + o_r64;
+        auto put = [&](size_t off, const void* src, size_t bytes) -> const void* { if (!src || !bytes) return nullptr; std::memcpy(r64 + off, src, bytes); return dv0 + o_r64 + off; };
+        if (NQ) { std::memcpy(r32, rw->queue, (size_t)NQ * 4); rv.queue = reinterpret_cast<const int32_t*>(dv0 + o_r32);
+                  if (rw->queue_priority) { std::memcpy(r32 + NQ, rw->queue_priority, (size_t)NQ * 4); rv.prio = reinterpret_cast<const int32_t*>(dv0 + o_r32) + NQ; } }
+        if (NJ) { std::memcpy(r32 + 2 * NQ, rw->job, (size_t)NJ * 4); rv.job = reinterpret_cast<const int32_t*>(dv0 + o_r32) + 2 * NQ; }
+        const size_t q3 = (size_t)3 * NQ * 8, q1 = (size_t)NQ * 8;
+        rv.deserved = static_cast<const double*>(put(0, rw ? rw->queue_deserved : nullptr, q3)); rv.limit = static_cast<const double*>(put(q3, rw ? rw->queue_limit : nullptr, q3));
+        rv.oqw = static_cast<const double*>(put(2 * q3, rw ? rw->queue_oqw : nullptr, q3)); rv.usage = static_cast<const double*>(put(3 * q3, rw ? rw->queue_usage : nullptr, q3));
+        rv.preempt_mr = static_cast<const int64_t*>(put(4 * q3, rw ? rw->queue_preempt_min_runtime_ns : nullptr, q1));
+        rv.reclaim_mr = static_cast<const int64_t*>(put(4 * q3 + q1, rw ? rw->queue_reclaim_min_runtime_ns : nullptr, q1));
+        rv.last_start = static_cast<const int64_t*>(put(4 * q3 + 2 * q1, rw ? rw->job_last_start_ns : nullptr, (size_t)NJ * 8));
     }
     unsigned char* dv = core->dl_dev;
     DeltaView v{reinterpret_cast<const int32_t*>(dv), reinterpret_cast<const int32_t*>(dv) + NP, reinterpret_cast<const int32_t*>(dv) + 2 * NP, reinterpret_cast<const int32_t*>(dv) + 3 * NP,
@@ -1106,6 +1126,15 @@ static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote)
     const bool cls_changed = prep.classes.size() != old_classes.size() || (!prep.classes.empty() && std::memcmp(prep.classes.data(), old_classes.data(), prep.classes.size() * sizeof(ClassRec)) != 0);
     if (dl->node_allocatable && NN) prep.exact_sums = prep.eval_exact_sums(R);  // (only node rows move the guard: the pods' requests are the snapshot's)
     prep.batch_ok = core->cfg.engine_mode == 0 && R <= 4 && prep.n_heights <= 16 && prep.exact_sums;
+    // the rows: the clock, and the queues' shares as the open of S' builds them (the only thing the host preparation derives from the rows)
+    if (rw && (rw->fields & KAI_ROWS_HAS_NOW)) { core->cfg.now_ns = rw->now_ns; c.now_ns = rw->now_ns; }
+    for (int i = 0; i < NQ; i++) for (int k = 0; k < 3; k++) {
+        QShare& x = prep.shares[(size_t)rw->queue[i] * 3 + k]; const size_t at = (size_t)k * NQ + i;
+        if (rw->queue_deserved) x.deserved = kd_quota_row(k, rw->queue_deserved[at]);
+        if (rw->queue_limit) x.max_allowed = kd_quota_row(k, rw->queue_limit[at]);
+        if (rw->queue_oqw) x.oqw = rw->queue_oqw[at];
+        if (rw->queue_usage) x.usage = rw->queue_usage[at];
+    }
     // ---- (5) the device: the scatter (the legacy-MIG nodes outside the delta as a second, small copy), the class labels, the session math
     const auto t2 = std::chrono::steady_clock::now();
     const int NX = NN + (int)extra.size();
@@ -1128,6 +1157,21 @@ static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote)
     HIP_TRY(core, hipGetLastError());
     int rc;
 #define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    if (NQ + NJ) {
+        // an array that was NULL at the open and gets its first rows: S' has it, with the value an absent array stands for in every other row.  The context points at a
+        // new array from here on (mr_on() switches on the presence of j_last_start), and the victim actions' replicas are laid out again, as when the class table grows.
+        auto fresh = [&](auto& field, size_t n, int byte) -> int {
+            const int rcf = dalloc_f(core, field, n); if (rcf) return rcf;
+            HIP_TRY(core, hipMemsetAsync(KAI_VP(field), byte, std::max<size_t>(n, 1) * sizeof(*field), core->stream));
+            core->mw_world = 0; return KAI_OK;
+        };
+        if (rv.last_start && !c.j_last_start) TRY(fresh(c.j_last_start, (size_t)c.J, 0));
+        if (rv.preempt_mr && !c.q_preempt_mr) TRY(fresh(c.q_preempt_mr, (size_t)c.Q, 0xFF));
+        if (rv.reclaim_mr && !c.q_reclaim_mr) TRY(fresh(c.q_reclaim_mr, (size_t)c.Q, 0xFF));
+        hipLaunchKernelGGL(k_apply_rows, dim3((NQ + NJ + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, rv, core->d_shares0, (int32_t*)KAI_VP(c.q_prio),
+                           (int64_t*)KAI_VP(c.q_preempt_mr), (int64_t*)KAI_VP(c.q_reclaim_mr), (int64_t*)KAI_VP(c.j_last_start));
+        HIP_TRY(core, hipGetLastError());
+    }
     if (cls_changed || remap_changed) {
         const int C = (int)prep.classes.size();
         if (C > core->cls_cap) {  // more classes than the session's arrays hold: new ones for KAI_CMAX (the victim actions' replicas are laid out again)
@@ -1185,37 +1229,54 @@ static int update_impl(kai_core* core, const kai_session_delta* dl, bool& wrote)
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     core->err = "ok";
     if (prof) { const auto t3 = std::chrono::steady_clock::now();
-                std::fprintf(stderr, "kai update: %d pods %d nodes | stage + gather + checks %.3f, host bookkeeping %.3f, device (scatter, classes, re-derivation) %.3f | total %.3f ms\n",
-                             NP, NN, tms(t0, t1), tms(t1, t2), tms(t2, t3), tms(t0, t3)); }
+                std::fprintf(stderr, "kai update: %d pods %d nodes %d queue rows %d job rows | stage + gather + checks %.3f, host bookkeeping %.3f, device (scatter, classes, re-derivation) %.3f | total %.3f ms\n",
+                             NP, NN, NQ, NJ, tms(t0, t1), tms(t1, t2), tms(t2, t3), tms(t0, t3)); }
     return KAI_OK;
 }
 
-int kai_session_update(kai_core* core, const kai_session_delta* d) {
-    if (!core) return KAI_ERR_INVALID_ARG;
-    if (!d) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: NULL delta");
-    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
-    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_session_update: a handle of a sharded group (open the new snapshot on every rank)");
-    if (d->version != KAI_DELTA_VERSION) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: wrong delta version");
-    const int N = core->ctx.N, P = core->ctx.P, NP = d->n_pods, NN = d->n_nodes;
-    if (NP < 0 || NN < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: negative count");
-    if (NP > 0 && (!d->pod || !d->pod_status || !d->pod_node)) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a required pod array is NULL");
-    if (NN > 0 && !d->node) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: the node array is NULL");
-    try {
+// the arguments of both parts, checked on the host before anything is written or sent (what: the entry point's name, for the messages)
+static int check_update_args(kai_core* core, const kai_session_delta* d, const kai_session_rows* r, const std::string& what) {
+    auto bad = [&](const char* m) { core->err = what + ": " + m; return (int)KAI_ERR_INVALID_ARG; };
+    const int N = core->ctx.N, P = core->ctx.P, J = core->ctx.J, Q = core->ctx.Q;
+    auto twice = [](const int32_t* x, int n) { std::vector<int32_t> a(x, x + n); std::sort(a.begin(), a.end()); return std::adjacent_find(a.begin(), a.end()) != a.end(); };
+    if (d) {
+        if (d->version != KAI_DELTA_VERSION) return bad("wrong delta version");
+        const int NP = d->n_pods, NN = d->n_nodes;
+        if (NP < 0 || NN < 0) return bad("negative count");
+        if (NP > 0 && (!d->pod || !d->pod_status || !d->pod_node)) return bad("a required pod array is NULL");
+        if (NN > 0 && !d->node) return bad("the node array is NULL");
         for (int i = 0; i < NP; i++) {
-            if (d->pod[i] < 0 || d->pod[i] >= P) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: pod index out of range");
-            if (d->pod_node[i] < -1 || d->pod_node[i] >= N) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: pod_node out of range");
+            if (d->pod[i] < 0 || d->pod[i] >= P) return bad("pod index out of range");
+            if (d->pod_node[i] < -1 || d->pod_node[i] >= N) return bad("pod_node out of range");
         }
-        for (int k = 0; k < NN; k++) if (d->node[k] < 0 || d->node[k] >= N) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: node index out of range");
-        {   std::vector<int32_t> a(d->pod, d->pod + NP); std::sort(a.begin(), a.end());
-            if (std::adjacent_find(a.begin(), a.end()) != a.end()) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a pod is listed twice");
-            std::vector<int32_t> b(d->node, d->node + NN); std::sort(b.begin(), b.end());
-            if (std::adjacent_find(b.begin(), b.end()) != b.end()) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: a node is listed twice"); }
-    } catch (const std::bad_alloc&) { core->err = "kai_session_update: out of host memory"; return KAI_ERR_NO_MEMORY; }
+        for (int k = 0; k < NN; k++) if (d->node[k] < 0 || d->node[k] >= N) return bad("node index out of range");
+        if (twice(d->pod, NP)) return bad("a pod is listed twice");
+        if (twice(d->node, NN)) return bad("a node is listed twice");
+    }
+    if (r) {  // (the open reads the rows' values as they are — it refuses none of them — so there is nothing to refuse in a value here either)
+        if (r->version != KAI_ROWS_VERSION) return bad("wrong rows version");
+        if (r->fields & ~KAI_ROWS_HAS_NOW) return bad("unknown bits in rows.fields");
+        const int NQ = r->n_queues, NJ = r->n_jobs;
+        if (NQ < 0 || NJ < 0) return bad("negative count");
+        if (NQ > 0 && !r->queue) return bad("the queue index array is NULL");
+        if (NJ > 0 && !r->job) return bad("the job index array is NULL");
+        for (int i = 0; i < NQ; i++) if (r->queue[i] < 0 || r->queue[i] >= Q) return bad("queue index out of range");
+        for (int i = 0; i < NJ; i++) if (r->job[i] < 0 || r->job[i] >= J) return bad("job index out of range");
+        if (twice(r->queue, NQ)) return bad("a queue is listed twice");
+        if (twice(r->job, NJ)) return bad("a job is listed twice");
+    }
+    return KAI_OK;
+}
+
+static int session_update(kai_core* core, const kai_session_delta* d, const kai_session_rows* r, const char* what) {
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (core->world > 1) { core->err = std::string(what) + ": a handle of a sharded group (open the new snapshot on every rank)"; return KAI_ERR_UNSUPPORTED; }
+    static const kai_session_delta no_delta = {KAI_DELTA_VERSION, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
     bool wrote = false; int rc;
-    try { rc = update_impl(core, d, wrote); }
-    catch (const std::bad_alloc&) { core->err = "kai_session_update: out of host memory"; rc = KAI_ERR_NO_MEMORY; }
-    catch (const std::exception& e) { core->err = std::string("kai_session_update: ") + e.what(); rc = KAI_ERR_INVALID_ARG; }
-    catch (...) { core->err = "kai_session_update: unknown exception"; rc = KAI_ERR_INVALID_ARG; }
+    try { rc = check_update_args(core, d, r, what); if (rc == KAI_OK) rc = update_impl(core, d ? d : &no_delta, r, wrote); }
+    catch (const std::bad_alloc&) { core->err = std::string(what) + ": out of host memory"; rc = KAI_ERR_NO_MEMORY; }
+    catch (const std::exception& e) { core->err = std::string(what) + ": " + e.what(); rc = KAI_ERR_INVALID_ARG; }
+    catch (...) { core->err = std::string(what) + ": unknown exception"; rc = KAI_ERR_INVALID_ARG; }
     if (rc != KAI_OK && wrote) {  // the writes began: the session is no longer the snapshot it was, nor S' — closed, as a failed open leaves it
         const std::string why = core->err;
         if (core->stream) (void)hipStreamSynchronize(core->stream);
@@ -1223,6 +1284,30 @@ int kai_session_update(kai_core* core, const kai_session_delta* d) {
         core->err = why;
     } else if (rc != KAI_OK && core->stream) (void)hipStreamSynchronize(core->stream);
     return rc;
+}
+
+int kai_session_update(kai_core* core, const kai_session_delta* d) {
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (!d) return fail(core, KAI_ERR_INVALID_ARG, "kai_session_update: NULL delta");
+    return session_update(core, d, nullptr, "kai_session_update");
+}
+
+int kai_session_update_rows(kai_core* core, const kai_session_delta* delta, const kai_session_rows* rows) {
+    if (!core) return KAI_ERR_INVALID_ARG;
+    return session_update(core, delta, rows, "kai_session_update_rows");
+}
+
+// The cycle's clock.  Every action sends the context again (kai_action_execute) and builds the replicas' contexts from it (prepare_multi), so the handle's copy is the one
+// that counts; the device copy follows for whatever reads it before the next action.
+int kai_core_set_now(kai_core* core, int64_t now_ns) {
+    if (!core) return KAI_ERR_INVALID_ARG;
+    core->cfg.now_ns = now_ns;
+    if (!core->open) return KAI_OK;
+    core->ctx.now_ns = now_ns;
+    HIP_TRY(core, hipSetDevice(core->device));
+    HIP_TRY(core, hipMemcpyAsync(core->d_ctx, &core->ctx, sizeof(KaiCtx), hipMemcpyHostToDevice, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    return KAI_OK;
 }
 
 int kai_queue_shares(kai_core* core, kai_queue_share* out, int cap) {

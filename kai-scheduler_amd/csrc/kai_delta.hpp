@@ -1,4 +1,5 @@
-// kai_delta.hpp — kernels of kai_session_update (include/kai_core.h): a pod / node delta applied to the HBM-resident snapshot of an open session.
+// kai_delta.hpp — kernels of kai_session_update / kai_session_update_rows (include/kai_core.h): a pod / node delta, and the queue rows and job start times that change
+// between two cycles, applied to the HBM-resident snapshot of an open session.
 //
 // The host stages the delta in ONE pinned buffer and sends it with one copy (DeltaView: the arrays inside that buffer).  k_delta_gather reads what the
 // snapshot holds for every changed pod (status, node, shared-GPU group, flags) without writing the session, so that every refusal is decided before the
@@ -6,6 +7,8 @@
 // adjusts the pending pods per request key itself, from the old statuses gathered here).  k_apply_delta then
 // scatters the delta into the baselines kai_session_reset restores (d_status0 / d_node0 / d_group0) and into the nodes' allocatable rows and flags,
 // mapping the caller's node indices through the name-rank permutation.  k_class_remap re-labels every pod's scan class when the class table changed.
+// k_apply_rows scatters the rows (RowsView: further arrays of the same buffer) into the QShare baseline, the queues' priorities and min-runtime settings and the jobs'
+// last start times; nothing on the host or the device is derived from those except what kai_session_reset's kernels compute again after every scatter.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,6 +73,46 @@ __global__ void __launch_bounds__(KD_TB) k_apply_delta(DeltaView d, int32_t* __r
         const int k = i - d.n_pods, e = (int)d.rank[d.node[k]];
         n_flags[e] = d.node_flags[k];
         for (int r = 0; r < d.R; r++) n_alloc[(size_t)r * d.N + e] = d.node_alloc[(size_t)r * d.n_nodes + k];
+    }
+}
+
+// The rows of kai_session_update_rows as they sit in the same staging buffer, behind the pod / node delta (one upload for both).  A quantity the call leaves
+// unchanged is a null pointer here; the index arrays were range-checked by the host and hold no index twice.
+struct RowsView {
+    const int32_t* queue; const double* deserved; const double* limit; const double* oqw; const double* usage;  // [n_queues]; the four quantities [3][n_queues], units of the snapshot's
+    const int32_t* prio; const int64_t* preempt_mr; const int64_t* reclaim_mr;
+    const int32_t* job; const int64_t* last_start;  // [n_jobs]
+    int32_t n_queues, n_jobs;
+};
+
+// A queue's deserved / limit value of resource k as the open stores it (HostPrep::build, proportion.createQueueResourceAttrs): memory in bytes, "unlimited" kept.
+// One multiplication and one compare, the same on the host and on the device: a row written here equals the one an open builds bit for bit.
+KAI_HD double kd_quota_row(int k, double v) {
+    if (k != KAI_Q_MEM) return v;
+    const double x = v * 1000000.0;
+    return KAI_UNLIMITED < x ? x : KAI_UNLIMITED;
+}
+
+// The scatter of the rows: one thread per changed queue writes its rows into the QShare baseline kai_session_reset restores (q * 3 + k), its priority and its
+// min-runtime settings; behind the queues one thread per changed job writes its last start time.
+__global__ void __launch_bounds__(KD_TB) k_apply_rows(RowsView v, QShare* __restrict__ shares0, int32_t* __restrict__ q_prio, int64_t* __restrict__ q_preempt_mr,
+                                                      int64_t* __restrict__ q_reclaim_mr, int64_t* __restrict__ j_last_start) {
+    const int i = blockIdx.x * KD_TB + threadIdx.x;
+    if (i < v.n_queues) {
+        const int q = v.queue[i];
+        for (int k = 0; k < 3; k++) {
+            QShare& x = shares0[(size_t)q * 3 + k]; const size_t at = (size_t)k * v.n_queues + i;
+            if (v.deserved) x.deserved = kd_quota_row(k, v.deserved[at]);
+            if (v.limit) x.max_allowed = kd_quota_row(k, v.limit[at]);
+            if (v.oqw) x.oqw = v.oqw[at];
+            if (v.usage) x.usage = v.usage[at];
+        }
+        if (v.prio) q_prio[q] = v.prio[i];
+        if (v.preempt_mr) q_preempt_mr[q] = v.preempt_mr[i];
+        if (v.reclaim_mr) q_reclaim_mr[q] = v.reclaim_mr[i];
+    } else if (i < v.n_queues + v.n_jobs) {
+        const int k = i - v.n_queues;
+        if (v.last_start) j_last_start[v.job[k]] = v.last_start[k];
     }
 }
 

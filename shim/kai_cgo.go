@@ -23,6 +23,7 @@ import "C"
 import (
 	"fmt"
 	"sort"
+	"time"
 	"unsafe"
 
 	v1 "k8s.io/api/core/v1"
@@ -434,8 +435,11 @@ type packParams struct{ schedulerName, gpuWorkerLabel, cpuWorkerLabel string }
 type plugin struct {
 	params packParams
 	pack   *packedSnapshot
-	prev   *packedSnapshot // the last cycle's pack, whose session stays open: the next cycle sends a delta against it (kai_session_update)
+	prev   *packedSnapshot // the last cycle's pack, whose session stays open: the next cycle sends a delta against it (kai_session_update_rows)
 }
+
+// Now is the cycle's clock (the minruntime plugin's "now"); a test replaces it.
+var Now = time.Now
 
 var current *plugin
 
@@ -446,11 +450,14 @@ func New(args framework.PluginArguments) framework.Plugin {
 func (p *plugin) Name() string { return "gpucore" }
 func (p *plugin) OnSessionOpen(ssn *framework.Session) { // framework/interface.go:49-55
 	p.pack = packSnapshot(ssn, p.params)
-	// Between two cycles most of the snapshot stays the same: when the new pack differs from the last one only in pod status / node / shared-GPU group
-	// and node flags / allocatable, the open session takes a delta (cost in proportion to the change) instead of the whole snapshot.
+	// The cycle's clock, every cycle, before the session is opened or updated: kai_config.now_ns of Init was only the first cycle's.
+	C.kai_core_set_now(core, C.int64_t(Now().UnixNano()))
+	// Between two cycles most of the snapshot stays the same: when the new pack differs from the last one only in pod status / node / shared-GPU group,
+	// node flags / allocatable, queue rows (quota, limit, over-quota weight, usage, priority, min-runtimes) and the jobs' last start times, the open session
+	// takes a delta and the changed rows (cost in proportion to the change) instead of the whole snapshot.
 	if p.prev != nil && !p.prev.fallback && sameStructure(p.prev, p.pack) {
 		d := packDelta(p.prev, p.pack)
-		rc := C.kai_session_update(core, &d.delta)
+		rc := C.kai_session_update_rows(core, &d.delta, &d.rows)
 		d.free()
 		if rc == 0 {
 			p.dropPrev()
@@ -479,9 +486,10 @@ func (p *plugin) dropPrev() {
 	}
 }
 
-// ------------------------------------------------------------------------------------------------ session delta (kai_session_update)
+// ------------------------------------------------------------------------------------------------ session delta (kai_session_update_rows)
 type packedDelta struct {
 	delta  C.kai_session_delta
+	rows   C.kai_session_rows
 	allocs []unsafe.Pointer
 }
 
@@ -500,7 +508,8 @@ func bytesOf[T any](p *T, n int) []byte {
 	return unsafe.Slice((*byte)(unsafe.Pointer(p)), n*int(unsafe.Sizeof(zero)))
 }
 
-// the same snapshot structure: the same counts and every array except pod status / node / shared-GPU group and node flags / allocatable byte for byte equal
+// the same snapshot structure: the same counts and every array byte for byte equal, except what the delta carries (pod status / node / shared-GPU group, node
+// flags / allocatable) and what the rows carry (queue deserved / limit / oqw / usage / priority / min-runtimes, job last start)
 func sameStructure(a, b *packedSnapshot) bool {
 	x, y := &a.soa, &b.soa
 	if x.n_res != y.n_res || x.n_nodes != y.n_nodes || x.n_pods != y.n_pods || x.n_podsets != y.n_podsets || x.n_jobs != y.n_jobs || x.n_queues != y.n_queues ||
@@ -525,12 +534,9 @@ func sameStructure(a, b *packedSnapshot) bool {
 		eq(bytesOf(x.job_uid_rank, J), bytesOf(y.job_uid_rank, J)) && eq(bytesOf(x.job_first_pod, J), bytesOf(y.job_first_pod, J)) &&
 		eq(bytesOf(x.job_n_pods, J), bytesOf(y.job_n_pods, J)) && eq(bytesOf(x.job_first_podset, J), bytesOf(y.job_first_podset, J)) &&
 		eq(bytesOf(x.job_n_podsets, J), bytesOf(y.job_n_podsets, J)) && eq(bytesOf(x.job_signature, J), bytesOf(y.job_signature, J)) &&
-		eq(bytesOf(x.job_last_start_ns, J), bytesOf(y.job_last_start_ns, J)) && eq(bytesOf(x.job_root_group, J), bytesOf(y.job_root_group, J)) &&
-		eq(bytesOf(x.queue_parent, Q), bytesOf(y.queue_parent, Q)) && eq(bytesOf(x.queue_priority, Q), bytesOf(y.queue_priority, Q)) &&
+		eq(bytesOf(x.job_root_group, J), bytesOf(y.job_root_group, J)) &&
+		eq(bytesOf(x.queue_parent, Q), bytesOf(y.queue_parent, Q)) &&
 		eq(bytesOf(x.queue_created_ns, Q), bytesOf(y.queue_created_ns, Q)) && eq(bytesOf(x.queue_uid_rank, Q), bytesOf(y.queue_uid_rank, Q)) &&
-		eq(bytesOf(x.queue_deserved, 3*Q), bytesOf(y.queue_deserved, 3*Q)) && eq(bytesOf(x.queue_limit, 3*Q), bytesOf(y.queue_limit, 3*Q)) &&
-		eq(bytesOf(x.queue_oqw, 3*Q), bytesOf(y.queue_oqw, 3*Q)) && eq(bytesOf(x.queue_usage, 3*Q), bytesOf(y.queue_usage, 3*Q)) &&
-		eq(bytesOf(x.queue_preempt_min_runtime_ns, Q), bytesOf(y.queue_preempt_min_runtime_ns, Q)) && eq(bytesOf(x.queue_reclaim_min_runtime_ns, Q), bytesOf(y.queue_reclaim_min_runtime_ns, Q)) &&
 		eq(bytesOf(x.class_fit, int(x.n_pod_classes)*int(x.n_node_classes)), bytesOf(y.class_fit, int(y.n_pod_classes)*int(y.n_node_classes))) &&
 		eq(bytesOf(x.topo_level_off, Tn+1), bytesOf(y.topo_level_off, Tn+1)) && eq(bytesOf(x.node_domain, TL*N), bytesOf(y.node_domain, TL*N)) &&
 		eq(bytesOf(x.domain_level, D), bytesOf(y.domain_level, D)) && eq(bytesOf(x.domain_parent, D), bytesOf(y.domain_parent, D)) && eq(bytesOf(x.domain_id_rank, D), bytesOf(y.domain_id_rank, D)) &&
@@ -540,12 +546,17 @@ func sameStructure(a, b *packedSnapshot) bool {
 		eq(bytesOf(x.podset_group, S), bytesOf(y.podset_group, S)) && eq(bytesOf(x.podset_topology, S), bytesOf(y.podset_topology, S)) &&
 		eq(bytesOf(x.podset_required_level, S), bytesOf(y.podset_required_level, S)) && eq(bytesOf(x.podset_preferred_level, S), bytesOf(y.podset_preferred_level, S)) &&
 		eq(bytesOf(x.res_mig_gpus, R), bytesOf(y.res_mig_gpus, R)) && eq(bytesOf(x.res_mig_memory, R), bytesOf(y.res_mig_memory, R))
-	// an optional array present in one pack and absent in the other is a structural change too (the pod_gpu_group array travels in the delta)
+	// an optional array present in one pack and absent in the other is a structural change too (the pod_gpu_group array travels in the delta; an array of the
+	// rows may appear, the library then creates it — but it cannot go away again)
+	gone := func(u, v unsafe.Pointer) bool { return u != nil && v == nil }
 	return same && (x.pod_gpu_portion == nil) == (y.pod_gpu_portion == nil) && (x.pod_gpu_memory == nil) == (y.pod_gpu_memory == nil) &&
-		(x.node_gpu_memory == nil) == (y.node_gpu_memory == nil) && (x.job_signature == nil) == (y.job_signature == nil)
+		(x.node_gpu_memory == nil) == (y.node_gpu_memory == nil) && (x.job_signature == nil) == (y.job_signature == nil) &&
+		!gone(unsafe.Pointer(x.queue_usage), unsafe.Pointer(y.queue_usage)) && !gone(unsafe.Pointer(x.job_last_start_ns), unsafe.Pointer(y.job_last_start_ns)) &&
+		!gone(unsafe.Pointer(x.queue_preempt_min_runtime_ns), unsafe.Pointer(y.queue_preempt_min_runtime_ns)) &&
+		!gone(unsafe.Pointer(x.queue_reclaim_min_runtime_ns), unsafe.Pointer(y.queue_reclaim_min_runtime_ns))
 }
 
-// the pods and nodes whose status / node / group or flags / allocatable differ between the two packs, in C memory
+// the pods and nodes whose status / node / group or flags / allocatable differ between the two packs, and the queues and jobs whose rows differ, in C memory
 func packDelta(a, b *packedSnapshot) *packedDelta {
 	x, y := &a.soa, &b.soa
 	N, P, R := int(y.n_nodes), int(y.n_pods), int(y.n_res)
@@ -600,7 +611,86 @@ func packDelta(a, b *packedSnapshot) *packedDelta {
 		d.delta.pod_gpu_group = &gr[0]
 	}
 	d.delta.n_nodes, d.delta.node, d.delta.node_flags, d.delta.node_allocatable = C.int32_t(nn), &node[0], &fl[0], &al[0]
+	packRows(d, x, y, alloc)
 	return d
+}
+
+// The queue and job rows that differ (kai_session_rows).  A changed queue sends all of its rows; an optional array the new pack lacks stays NULL (sameStructure
+// has made sure the old pack lacked it too), one the old pack lacked reads as the value an absent array stands for.
+func packRows(d *packedDelta, x, y *C.kai_snapshot_soa, alloc func(int) unsafe.Pointer) {
+	Q, J := int(y.n_queues), int(y.n_jobs)
+	f64 := func(p *C.double, n, i int, absent C.double) C.double {
+		if p == nil {
+			return absent
+		}
+		return unsafe.Slice(p, n)[i]
+	}
+	i64 := func(p *C.int64_t, n, i int, absent C.int64_t) C.int64_t {
+		if p == nil {
+			return absent
+		}
+		return unsafe.Slice(p, n)[i]
+	}
+	var queues, jobs []int
+	for q := 0; q < Q; q++ {
+		diff := unsafe.Slice(x.queue_priority, Q)[q] != unsafe.Slice(y.queue_priority, Q)[q] ||
+			i64(x.queue_preempt_min_runtime_ns, Q, q, -1) != i64(y.queue_preempt_min_runtime_ns, Q, q, -1) ||
+			i64(x.queue_reclaim_min_runtime_ns, Q, q, -1) != i64(y.queue_reclaim_min_runtime_ns, Q, q, -1)
+		for k := 0; k < 3 && !diff; k++ {
+			at := k*Q + q
+			diff = f64(x.queue_deserved, 3*Q, at, 0) != f64(y.queue_deserved, 3*Q, at, 0) || f64(x.queue_limit, 3*Q, at, 0) != f64(y.queue_limit, 3*Q, at, 0) ||
+				f64(x.queue_oqw, 3*Q, at, 0) != f64(y.queue_oqw, 3*Q, at, 0) || f64(x.queue_usage, 3*Q, at, 0) != f64(y.queue_usage, 3*Q, at, 0)
+		}
+		if diff {
+			queues = append(queues, q)
+		}
+	}
+	for j := 0; j < J; j++ {
+		if i64(x.job_last_start_ns, J, j, 0) != i64(y.job_last_start_ns, J, j, 0) {
+			jobs = append(jobs, j)
+		}
+	}
+	r := &d.rows
+	r.version = C.KAI_ROWS_VERSION
+	nq, nj := len(queues), len(jobs)
+	if nq > 0 {
+		qi := unsafe.Slice((*C.int32_t)(alloc(4*nq)), nq)
+		pr := unsafe.Slice((*C.int32_t)(alloc(4*nq)), nq)
+		quad := [4][]C.double{}
+		for a := range quad {
+			quad[a] = unsafe.Slice((*C.double)(alloc(8*3*nq)), 3*nq)
+		}
+		mr := [2][]C.int64_t{unsafe.Slice((*C.int64_t)(alloc(8*nq)), nq), unsafe.Slice((*C.int64_t)(alloc(8*nq)), nq)}
+		src := [4]*C.double{y.queue_deserved, y.queue_limit, y.queue_oqw, y.queue_usage}
+		for i, q := range queues {
+			qi[i], pr[i] = C.int32_t(q), unsafe.Slice(y.queue_priority, Q)[q]
+			for a := range quad {
+				for k := 0; k < 3; k++ {
+					quad[a][k*nq+i] = f64(src[a], 3*Q, k*Q+q, 0)
+				}
+			}
+			mr[0][i], mr[1][i] = i64(y.queue_preempt_min_runtime_ns, Q, q, -1), i64(y.queue_reclaim_min_runtime_ns, Q, q, -1)
+		}
+		r.n_queues, r.queue, r.queue_priority = C.int32_t(nq), &qi[0], &pr[0]
+		r.queue_deserved, r.queue_limit, r.queue_oqw = &quad[0][0], &quad[1][0], &quad[2][0]
+		if y.queue_usage != nil {
+			r.queue_usage = &quad[3][0]
+		}
+		if y.queue_preempt_min_runtime_ns != nil {
+			r.queue_preempt_min_runtime_ns = &mr[0][0]
+		}
+		if y.queue_reclaim_min_runtime_ns != nil {
+			r.queue_reclaim_min_runtime_ns = &mr[1][0]
+		}
+	}
+	if nj > 0 { // (a differing row means the new pack has the array)
+		ji := unsafe.Slice((*C.int32_t)(alloc(4*nj)), nj)
+		ls := unsafe.Slice((*C.int64_t)(alloc(8*nj)), nj)
+		for i, j := range jobs {
+			ji[i], ls[i] = C.int32_t(j), unsafe.Slice(y.job_last_start_ns, J)[j]
+		}
+		r.n_jobs, r.job, r.job_last_start_ns = C.int32_t(nj), &ji[0], &ls[0]
+	}
 }
 
 // ------------------------------------------------------------------------------------------------ framework.Action

@@ -50,7 +50,7 @@ func ConfigFromScheduler(sc *conf.SchedulerConfiguration, params conf.SchedulerP
 	cfg.use_scheduling_signatures = b2i(params.UseSchedulingSignatures)
 	cfg.allow_consolidating_reclaim = b2i(params.AllowConsolidatingReclaim)
 	cfg.full_hierarchy_fairness = b2i(params.FullHierarchyFairness)
-	cfg.now_ns = C.int64_t(now.UnixNano())
+	cfg.now_ns = C.int64_t(now.UnixNano()) // only the FIRST cycle's clock: OnSessionOpen moves it every cycle (kai_core_set_now)
 	for i := range cfg.queue_depth { // framework/session.go:398-404: no entry = every job of the queue
 		cfg.queue_depth[i] = -1
 	}

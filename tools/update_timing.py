@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as _entry  # noqa: E402
 
 pkg = _entry._load_pkg()
-PROF = re.compile(r"kai update: (\d+) pods (\d+) nodes \| stage \+ gather \+ checks ([\d.]+), host bookkeeping ([\d.]+), device \(scatter, classes, re-derivation\) ([\d.]+) \| total ([\d.]+) ms")
+PROF = re.compile(r"kai update: (\d+) pods (\d+) nodes(?: \d+ queue rows \d+ job rows)? \| stage \+ gather \+ checks ([\d.]+), host bookkeeping ([\d.]+), device \(scatter, classes, re-derivation\) ([\d.]+) \| total ([\d.]+) ms")
 
 
 def ops_hash(ops):
