@@ -475,6 +475,23 @@ int kai_action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_
 int kai_best_node(kai_core* core, int32_t pod_idx, const uint32_t* nodeset_bitmap, int pipeline_only,
                   int32_t* node_idx_out, int* is_pipeline_out);
 
+/* kai_best_node for MANY tasks in one chip-wide pass: out[i] is exactly what
+ * kai_best_node(core, queries[i].pod, row queries[i].nodeset of nodeset_bitmaps or NULL, queries[i].flags & KAI_QUERY_PIPELINE_ONLY, ...)
+ * returns at the same session state — the same node (caller's index, -1 when nothing fits) and the same is_pipeline.  nodeset is a row of
+ * nodeset_bitmaps (n_nodesets rows of ceil(N/32) words, caller's node indices, the bit convention of kai_best_node) or -1 for all nodes; the
+ * tasks of one job usually share a row.  The call changes nothing: read-backs, kai_action_stats_get and every later action are as if it had
+ * not happened.  Like kai_best_node it does not look at the pod's status; duplicate queries are allowed.
+ * n_queries == 0: KAI_OK without a launch.  KAI_ERR_INVALID_ARG: a NULL array with a count above 0, a negative count, a pod out of range,
+ * a nodeset outside -1 .. n_nodesets-1, unknown flag bits, non-zero pad.  KAI_ERR_STATE: no open session.  KAI_ERR_UNSUPPORTED: a handle of
+ * a sharded group (n_gpus > 1).  Every refusal is decided before the first device call and leaves out untouched.
+ * On the device: one staging upload, three launches (k_bn_prep, k_bn_range, k_bn_scan; kai_best_nodes.hpp), one download and one stream
+ * synchronise; the scratch belongs to the handle, grows on demand and is freed by kai_core_destroy. */
+#define KAI_QUERY_PIPELINE_ONLY 0x1u
+typedef struct kai_node_query  { int32_t pod; int32_t nodeset; uint32_t flags; int32_t pad; } kai_node_query;
+typedef struct kai_node_answer { int32_t node; int32_t is_pipeline; } kai_node_answer;
+int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries,
+                   const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

@@ -215,6 +215,18 @@ class KaiOp(C.Structure):
     _fields_ = [("seq", C.c_int64), ("kind", C.c_int32), ("pod", C.c_int32), ("node", C.c_int32), ("job", C.c_int32), ("stmt", C.c_int32), ("pad", C.c_int32)]
 
 
+QUERY_PIPELINE_ONLY = 0x1  # KAI_QUERY_PIPELINE_ONLY
+
+
+class KaiNodeQuery(C.Structure):
+    """kai_node_query (include/kai_core.h): one task of kai_best_nodes; nodeset = a row of the call's bitmaps, -1 = all nodes."""
+    _fields_ = [("pod", C.c_int32), ("nodeset", C.c_int32), ("flags", C.c_uint32), ("pad", C.c_int32)]
+
+
+class KaiNodeAnswer(C.Structure):
+    _fields_ = [("node", C.c_int32), ("is_pipeline", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

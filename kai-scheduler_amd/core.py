@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -123,6 +123,7 @@ def load_library(path: str = LIB_PATH):
     lib.kai_queue_shares.argtypes = [C.c_void_p, C.POINTER(abi.KaiQueueShare), C.c_int]
     lib.kai_action_execute.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64)]
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
+    lib.kai_best_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiNodeAnswer)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -295,6 +296,34 @@ class Session:
             bits = words.ctypes.data_as(C.POINTER(C.c_uint32))
         self.core._check(self.core.lib.kai_best_node(self.core.handle, pod, bits, int(pipeline_only), C.byref(node), C.byref(pipe)))
         return node.value, bool(pipe.value)
+
+    def best_nodes(self, pods, nodesets=None, nodeset_of=None, pipeline_only=None):
+        """kai_best_nodes: best_node for many tasks in one chip-wide pass.  pods: pod indices; nodesets: node sets as index lists or boolean masks over the
+        nodes; nodeset_of: per pod its set in `nodesets` (-1 / None = all nodes); pipeline_only: one bool for all or one per pod.
+        Returns (node, is_pipeline): an int32 array (-1 = nothing fits) and a bool array."""
+        pods = np.ascontiguousarray(pods, dtype=np.int32).ravel()
+        M, N = len(pods), self.snap.n_nodes
+        W = (N + 31) // 32
+        sets = [] if nodesets is None else list(nodesets)
+        words = np.zeros((max(len(sets), 1), max(W, 1)), np.uint32)
+        for s, ns in enumerate(sets):
+            ns = np.asarray(ns)
+            idx = np.nonzero(ns)[0] if ns.dtype == np.bool_ else ns.astype(np.int64).ravel()
+            if ns.dtype == np.bool_ and len(ns) != N:
+                raise ValueError("a boolean node-set mask has one entry per node")
+            if len(idx) and (idx.min() < 0 or idx.max() >= N):
+                raise ValueError("node index out of range in a node set")
+            np.bitwise_or.at(words[s], idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
+        q = np.zeros(M, dtype=np.dtype([("pod", "<i4"), ("nodeset", "<i4"), ("flags", "<u4"), ("pad", "<i4")]))  # kai_node_query
+        q["pod"] = pods
+        q["nodeset"] = -1 if nodeset_of is None else np.array([-1 if s is None else int(s) for s in np.asarray(nodeset_of, dtype=object).ravel()], dtype=np.int32)
+        if pipeline_only is not None:
+            q["flags"] = np.where(np.broadcast_to(np.asarray(pipeline_only, dtype=bool), (M,)), abi.QUERY_PIPELINE_ONLY, 0)
+        out = np.zeros(M, dtype=np.dtype([("node", "<i4"), ("is_pipeline", "<i4")]))  # kai_node_answer
+        self.core._check(self.core.lib.kai_best_nodes(self.core.handle, q.ctypes.data_as(C.POINTER(abi.KaiNodeQuery)), M,
+                                                      words.ctypes.data_as(C.POINTER(C.c_uint32)) if sets else None, len(sets),
+                                                      out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer))))
+        return out["node"].copy(), out["is_pipeline"].astype(bool)
 
     def gpu_groups(self):
         """PodInfo.GPUGroups[0] of the active fraction pods (-1 elsewhere): kai_pod_gpu_groups."""

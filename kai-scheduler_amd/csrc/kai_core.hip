@@ -22,6 +22,7 @@
 #include "kai_batch_driver.hpp"
 #include "kai_victim_shard.hpp"
 #include "kai_delta.hpp"
+#include "kai_best_nodes.hpp"
 #include <map>
 #include <mutex>
 #include <thread>
@@ -103,6 +104,8 @@ struct kai_core {
     int cls_cap = 0;  // classes the session's cls / sum1_key / sum1_node arrays hold
     uint32_t* d_rank = nullptr; int32_t* d_pkey = nullptr; int32_t* d_remap = nullptr; size_t remap_cap = 0;  // first update of a session: name ranks, pods' request keys, key -> class
     unsigned char* dl_pin = nullptr; size_t dl_pin_bytes = 0; unsigned char* dl_dev = nullptr; size_t dl_dev_bytes = 0;  // the delta's staging: pinned and device, grows, lives with the handle
+    // kai_best_nodes (kai_best_nodes.hpp): pinned staging and device scratch, grow, live with the handle; whether the scratch holds this session's permutation; CUs of the device
+    unsigned char* bn_pin = nullptr; size_t bn_pin_bytes = 0; unsigned char* bn_dev = nullptr; size_t bn_dev_bytes = 0; bool bn_perm_ok = false; int bn_cus = 0;
 };
 
 #define HIP_TRY(core, expr)                                                                                        \
@@ -579,6 +582,8 @@ int kai_core_destroy(kai_core* core) {
     free_session(core, true);
     if (core->dl_pin) { (void)hipHostFree(core->dl_pin); core->dl_pin = nullptr; }
     if (core->dl_dev) { (void)hipFree(core->dl_dev); core->dl_dev = nullptr; }
+    if (core->bn_pin) { (void)hipHostFree(core->bn_pin); core->bn_pin = nullptr; core->bn_pin_bytes = 0; }
+    if (core->bn_dev) { (void)hipFree(core->bn_dev); core->bn_dev = nullptr; core->bn_dev_bytes = 0; }
     if (core->pin_buf) { (void)hipHostFree(core->pin_buf); core->pin_buf = nullptr; core->pin_bytes = 0; }
     if (core->up_pin) { (void)hipStreamSynchronize(core->stream); (void)hipHostFree(core->up_pin); core->up_pin = nullptr; core->up_pin_bytes = 0; }
     if (core->rccl_comm) { (void)hipStreamSynchronize(core->stream); if (RcclApi* a = rccl_api()) (void)a->CommDestroy(core->rccl_comm); core->rccl_comm = nullptr; }
@@ -679,7 +684,7 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     core->legacy_on = any_legacy_mig; core->legacy_cnt.clear();
     if (any_legacy_mig) { core->legacy_cnt.assign((size_t)N, 0); for (int p = 0; p < P; p++)  // NodeInfo.LegacyMIGTasks (node_info.go:407-409): a node that holds a legacy MIG task takes no MIG request
         if ((s->pod_flags[p] & KAI_POD_LEGACY_MIG) && prep.pod_node[p] >= 0 && (s->pod_status[p] & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING))) { prep.node_flags[prep.pod_node[p]] |= KAI_NODE_LEGACY_MIG_I; core->legacy_cnt[(size_t)prep.pod_node[p]]++; } }
-    core->perm = prep.perm;
+    core->perm = prep.perm; core->bn_perm_ok = false;
 
     int rc;
 #define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
@@ -1529,6 +1534,75 @@ int kai_best_node(kai_core* core, int32_t pod_idx, const uint32_t* nodeset_bitma
     if (d_bits) (void)hipFree(d_bits);
     *node_idx_out = h[0] >= 0 ? core->perm[h[0]] : -1;
     if (is_pipeline_out) *is_pipeline_out = h[1];
+    return KAI_OK;
+}
+
+int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out) {
+    // every refusal before the first device call; `out` is written only after the answers came back
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (n_queries < 0 || n_nodesets < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: a negative count");
+    if (n_queries > 0 && (!queries || !out)) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: queries / out is NULL");
+    if (n_nodesets > 0 && !nodeset_bitmaps) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: nodeset_bitmaps is NULL");
+    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_best_nodes: a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (n_queries == 0) return KAI_OK;
+    const int N = core->ctx.N, P = core->ctx.P, M = n_queries, S = n_nodesets, W = (N + 31) / 32;
+    for (int i = 0; i < M; i++) {
+        const kai_node_query& q = queries[i];
+        if (q.pod < 0 || q.pod >= P) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: pod index out of range");
+        if (q.nodeset < -1 || q.nodeset >= S) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: nodeset outside -1 .. n_nodesets-1");
+        if (q.flags & ~KAI_QUERY_PIPELINE_ONLY) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: unknown flag bits");
+        if (q.pad != 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: pad is not zero");
+    }
+    HIP_TRY(core, hipSetDevice(core->device));
+    const BnLayout L(N, M, S, W);
+    if (L.end > core->bn_dev_bytes) {  // scratch growth: the only allocation, none once the handle is warm
+        if (core->bn_dev) (void)hipFree(core->bn_dev);
+        core->bn_dev = nullptr; core->bn_dev_bytes = 0; core->bn_perm_ok = false;
+        const size_t want = std::max<size_t>(L.end + L.end / 2, (size_t)1 << 16);
+        HIP_TRY(core, hipMalloc(reinterpret_cast<void**>(&core->bn_dev), want));
+        core->bn_dev_bytes = want;
+    }
+    const size_t pin_need = L.up_end + (size_t)M * sizeof(kai_node_answer) + 16;  // [what is sent][the answers]
+    if (pin_need > core->bn_pin_bytes) {
+        if (core->bn_pin) (void)hipHostFree(core->bn_pin);
+        core->bn_pin = nullptr; core->bn_pin_bytes = 0;
+        const size_t want = std::max<size_t>(pin_need + pin_need / 2, (size_t)1 << 16);
+        HIP_TRY(core, hipHostMalloc(reinterpret_cast<void**>(&core->bn_pin), want, hipHostMallocDefault));
+        core->bn_pin_bytes = want;
+    }
+    if (core->bn_cus <= 0) { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, core->device) != hipSuccess || cus <= 0) cus = 64; core->bn_cus = cus; }
+    // ---- one staging upload: [queries | rows | zeroed need flags], behind the permutation when the scratch does not hold this session's yet
+    unsigned char* h = core->bn_pin; unsigned char* d = core->bn_dev;
+    const size_t up0 = core->bn_perm_ok ? L.queries : L.perm;
+    if (!core->bn_perm_ok && N > 0) std::memcpy(h + L.perm, core->perm.data(), (size_t)N * 4);
+    std::memcpy(h + L.queries, queries, (size_t)M * sizeof(kai_node_query));
+    if (S > 0 && W > 0) std::memcpy(h + L.rows_in, nodeset_bitmaps, (size_t)S * W * 4);
+    std::memset(h + L.need, 0, L.up_end - L.need);
+    HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, L.up_end - up0, hipMemcpyHostToDevice, core->stream));
+    core->bn_perm_ok = true;
+    BnArgs a{};
+    a.M = M; a.S = S; a.W = W;
+    a.queries = (KAI_GP(const kai_node_query))(d + L.queries); a.rows_in = (KAI_GP(const uint32_t))(d + L.rows_in); a.perm = (KAI_GP(const int32_t))(d + L.perm);
+    a.rows = (KAI_GP(uint32_t))(d + L.rows); a.need = (KAI_GP(int32_t))(d + L.need); a.range = (KAI_GP(double))(d + L.range);
+    a.prep = (KAI_GP(BnQuery))(d + L.prep); a.out = (KAI_GP(kai_node_answer))(d + L.out);
+    // ---- three launches
+    const size_t prep_items = std::max<size_t>((size_t)M, (size_t)S * W);
+    hipLaunchKernelGGL(k_bn_prep, dim3((unsigned)((prep_items + KAI_BN_WG - 1) / KAI_BN_WG)), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
+    HIP_TRY(core, hipGetLastError());
+    const bool binpack = (core->ctx.plugins & KAI_PLUGIN_NODEPLACEMENT) && (core->ctx.gpu_strategy == KAI_BINPACK || core->ctx.cpu_strategy == KAI_BINPACK);
+    if (binpack) {  // NodePreOrderFn exists with a bin-pack strategy only; workgroups of pairs no query needs leave at once
+        hipLaunchKernelGGL(k_bn_range, dim3((unsigned)(2 * (S + 1))), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
+        HIP_TRY(core, hipGetLastError());
+    }
+    const int grid = std::min(M, core->bn_cus * KAI_BN_WGS_PER_CU);
+    hipLaunchKernelGGL(k_bn_scan, dim3((unsigned)grid), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
+    HIP_TRY(core, hipGetLastError());
+    // ---- one download, one synchronise
+    unsigned char* h_out = h + L.up_end;
+    HIP_TRY(core, hipMemcpyAsync(h_out, d + L.out, (size_t)M * sizeof(kai_node_answer), hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    std::memcpy(out, h_out, (size_t)M * sizeof(kai_node_answer));
     return KAI_OK;
 }
 

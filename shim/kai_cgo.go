@@ -726,6 +726,88 @@ func (a *action) Execute(ssn *framework.Session) { // framework/interface.go:41-
 	}
 }
 
+// BestNodes: Session.OrderedNodesByTask + FittingNode (framework/session.go:201-264) for many tasks against the device's current session state, in ONE
+// kai_best_nodes call — what a Go action that stays on the host asks instead of one kai_best_node per task (a gang walked over a SubsetNodesFn result,
+// a "why is this pod pending" query over a queue).  nodeSets[i] is the node set of tasks[i] (nil = all nodes); tasks that share a slice (the tasks of one
+// job after SubsetNodesFn) share one bitmap row.  Returns per task the node (nil when nothing fits) and whether the placement would be a pipeline.
+// ok = false: no device session, a task or node the snapshot does not know, or a refusal — the caller asks the Go session instead.
+func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipelineOnly bool) (nodes []*node_info.NodeInfo, isPipeline []bool, ok bool) {
+	if current == nil || current.pack == nil || current.pack.fallback || len(nodeSets) != len(tasks) {
+		return nil, nil, false
+	}
+	pack := current.pack
+	if len(tasks) == 0 {
+		return nil, nil, true
+	}
+	podOf := make(map[*pod_info.PodInfo]int, len(pack.pods))
+	for i, t := range pack.pods {
+		podOf[t] = i
+	}
+	nodeOf := make(map[*node_info.NodeInfo]int, len(pack.nodes))
+	for i, n := range pack.nodes {
+		nodeOf[n] = i
+	}
+	words := (len(pack.nodes) + 31) / 32
+	type setKey struct { // slices of one backing array with one length are one node set; every empty set is the same set
+		first **node_info.NodeInfo
+		n     int
+	}
+	rows := map[setKey]int{}
+	var bitmaps []C.uint32_t
+	queries := make([]C.kai_node_query, len(tasks))
+	for i, t := range tasks {
+		p, known := podOf[t]
+		if !known {
+			return nil, nil, false
+		}
+		queries[i].pod = C.int32_t(p)
+		queries[i].nodeset = -1
+		if pipelineOnly {
+			queries[i].flags = C.KAI_QUERY_PIPELINE_ONLY
+		}
+		set := nodeSets[i]
+		if set == nil || words == 0 {
+			continue
+		}
+		key := setKey{nil, 0}
+		if len(set) > 0 {
+			key = setKey{&set[0], len(set)}
+		}
+		row, seen := rows[key]
+		if !seen {
+			row = len(bitmaps) / words
+			bitmaps = append(bitmaps, make([]C.uint32_t, words)...)
+			for _, n := range set {
+				ni, known := nodeOf[n]
+				if !known {
+					return nil, nil, false
+				}
+				bitmaps[row*words+ni>>5] |= 1 << (uint(ni) & 31)
+			}
+			rows[key] = row
+		}
+		queries[i].nodeset = C.int32_t(row)
+	}
+	nRows := 0
+	if words > 0 {
+		nRows = len(bitmaps) / words
+	}
+	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+	answers := make([]C.kai_node_answer, len(tasks))
+	if rc := C.kai_best_nodes(core, &queries[0], C.int32_t(len(queries)), ptr(bitmaps), C.int32_t(nRows), &answers[0]); rc != 0 {
+		return nil, nil, false
+	}
+	nodes = make([]*node_info.NodeInfo, len(tasks))
+	isPipeline = make([]bool, len(tasks))
+	for i, a := range answers {
+		if a.node >= 0 {
+			nodes[i] = pack.nodes[a.node]
+		}
+		isPipeline[i] = a.is_pipeline != 0
+	}
+	return nodes, isPipeline, true
+}
+
 // replay: the committed operations through the real Statement.  kai_op.stmt numbers the Statements of the action in
 // commit order; one id = one Statement, e.g. a reclaim "evict A, evict B, pipeline C" (framework/statement.go:536-575).
 // An operation the live session refuses (the cache moved on since the snapshot, a bind conflict) discards its whole Statement —
