@@ -492,6 +492,40 @@ typedef struct kai_node_answer { int32_t node; int32_t is_pipeline; } kai_node_a
 int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries,
                    const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out);
 
+/* Committed operations taken back INTO the open session: what framework.Statement does with them (framework/statement.go), for operations an action of this
+ * handle did not commit itself — an action the Go scheduler ran after a fallback, the operations of another handle (a standby scheduler, a what-if session).
+ * The operations are taken in array order.  Each maximal run of equal `stmt` is one Statement: KAI_OP_ALLOCATE is Statement.Allocate(pod, node),
+ * KAI_OP_PIPELINE is Statement.Pipeline(pod, node, updateTaskIfExistsOnNode = true), KAI_OP_EVICT is Statement.Evict(pod); the Statement is then
+ * committed, so an allocated pod ends up Binding.
+ *
+ * Contract.  After KAI_OK the handle is indistinguishable from one whose own actions had committed exactly these operations: kai_pod_states,
+ * kai_node_states and kai_queue_shares bit for bit, the same answers from kai_best_node(s), the same operations (kind, pod, node, job, stmt, seq) and
+ * state from every later kai_action_execute.  kai_session_reset and kai_session_update* discard applied operations as they discard action results;
+ * kai_action_stats_get is unaffected.
+ * Fields: `node` is the caller's node index (for an evict: the node the pod is evicted from); `seq` and `job` are not read, so the array
+ * kai_action_execute wrote can be passed as it is; `pad` must be 0; `stmt` must be non-decreasing.  Resource feasibility is not checked (Statement
+ * does not check it either).
+ * Per-operation precondition, against the state the preceding operations of the same call leave: ALLOCATE needs a Pending pod, PIPELINE a Pending or
+ * Releasing pod, EVICT a pod that has a node, and op.node must be that node.
+ * Every refusal is decided before the first write and leaves the session open and bit for bit unchanged; result->first_bad is the index of the first
+ * offending operation, -1 on success and where no single operation is at fault (NULL ops, a negative count, unknown flags bits).
+ *  - KAI_ERR_INVALID_ARG: NULL ops with n_ops > 0, a negative count, unknown flags bits, a kind outside 0..2, a pod or node index out of range, non-zero
+ *    pad, a decreasing stmt;  KAI_ERR_CAPACITY: more than 2^31 - 16 operations;
+ *  - KAI_ERR_STATE: no open session, or an operation whose precondition fails;
+ *  - KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1), or a session with shared-GPU requests (kai_op carries no GPU group).
+ *  n_ops == 0: KAI_OK without a device call.
+ * Two paths (kai_ops_apply.hpp), result->path says which one took the batch (with KAI_APPLY_CHECK_ONLY: which one would).  The chip-wide path takes a batch
+ * that names every pod once, allocates / pipelines Pending pods and evicts Allocated, Binding, Bound or Running ones, in a session whose quantities add
+ * exactly in any order (what the batch path of the allocate action asks for): one upload, two launches, one small download, one synchronise.  Everything
+ * else — a pod evicted and pipelined again in one call — is walked by one lane through the engine's own Statement functions. */
+#define KAI_APPLY_CHECK_ONLY  0x1u   /* validate, write nothing */
+#define KAI_APPLY_ENGINE_PATH 0x2u   /* take the engine walk even where the chip-wide path qualifies (tests, A/B) */
+#define KAI_APPLY_PATH_NONE 0
+#define KAI_APPLY_PATH_WIDE 1
+#define KAI_APPLY_PATH_ENGINE 2
+typedef struct kai_apply_result { int64_t first_bad; int32_t path; int32_t statements; } kai_apply_result;
+int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_apply_result* result /* may be NULL */);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

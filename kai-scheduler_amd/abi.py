@@ -227,6 +227,15 @@ class KaiNodeAnswer(C.Structure):
     _fields_ = [("node", C.c_int32), ("is_pipeline", C.c_int32)]
 
 
+APPLY_CHECK_ONLY, APPLY_ENGINE_PATH = 0x1, 0x2          # KAI_APPLY_CHECK_ONLY, KAI_APPLY_ENGINE_PATH
+APPLY_PATH_NONE, APPLY_PATH_WIDE, APPLY_PATH_ENGINE = 0, 1, 2  # kai_apply_result.path
+
+
+class KaiApplyResult(C.Structure):
+    """kai_apply_result (include/kai_core.h): what kai_ops_apply says about a batch — the first offending operation (-1 = none), the path that took it, its Statements."""
+    _fields_ = [("first_bad", C.c_int64), ("path", C.c_int32), ("statements", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

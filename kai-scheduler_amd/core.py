@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ops_apply",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -124,6 +124,7 @@ def load_library(path: str = LIB_PATH):
     lib.kai_action_execute.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64)]
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
     lib.kai_best_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiNodeAnswer)]
+    lib.kai_ops_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiApplyResult)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -324,6 +325,20 @@ class Session:
                                                       words.ctypes.data_as(C.POINTER(C.c_uint32)) if sets else None, len(sets),
                                                       out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer))))
         return out["node"].copy(), out["is_pipeline"].astype(bool)
+
+    def apply_ops(self, ops, check_only: bool = False, engine_path: bool = False):
+        """kai_ops_apply: committed operations taken back into the session, as framework.Statement applies and commits them — `ops` is the array `execute` returns
+        (of this or another handle), or any array of kai_op records (seq and job are not read).  check_only: validate, write nothing; engine_path: take the engine
+        walk even where the chip-wide path qualifies.  Returns the kai_apply_result; a refusal raises KaiError with the result as its `.result`."""
+        arr = np.ascontiguousarray(ops, dtype=_OP_DTYPE)
+        res = abi.KaiApplyResult()
+        flags = (abi.APPLY_CHECK_ONLY if check_only else 0) | (abi.APPLY_ENGINE_PATH if engine_path else 0)
+        rc = self.core.lib.kai_ops_apply(self.core.handle, arr.ctypes.data_as(C.POINTER(abi.KaiOp)) if len(arr) else None, len(arr), flags, C.byref(res))
+        if rc != 0:
+            err = KaiError(rc, self.core.lib.kai_last_error(self.core.handle).decode())
+            err.result = res
+            raise err
+        return res
 
     def gpu_groups(self):
         """PodInfo.GPUGroups[0] of the active fraction pods (-1 elsewhere): kai_pod_gpu_groups."""

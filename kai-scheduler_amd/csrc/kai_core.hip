@@ -23,6 +23,7 @@
 #include "kai_victim_shard.hpp"
 #include "kai_delta.hpp"
 #include "kai_best_nodes.hpp"
+#include "kai_ops_apply.hpp"
 #include <map>
 #include <mutex>
 #include <thread>
@@ -106,6 +107,8 @@ struct kai_core {
     unsigned char* dl_pin = nullptr; size_t dl_pin_bytes = 0; unsigned char* dl_dev = nullptr; size_t dl_dev_bytes = 0;  // the delta's staging: pinned and device, grows, lives with the handle
     // kai_best_nodes (kai_best_nodes.hpp): pinned staging and device scratch, grow, live with the handle; whether the scratch holds this session's permutation; CUs of the device
     unsigned char* bn_pin = nullptr; size_t bn_pin_bytes = 0; unsigned char* bn_dev = nullptr; size_t bn_dev_bytes = 0; bool bn_perm_ok = false; int bn_cus = 0;
+    // kai_ops_apply (kai_ops_apply.hpp): pinned staging and device scratch, grow, live with the handle; pods the scratch's per-pod arrays hold; caller's node index -> name rank (of this session's permutation)
+    unsigned char* oa_pin = nullptr; size_t oa_pin_bytes = 0; unsigned char* oa_dev = nullptr; size_t oa_dev_bytes = 0; size_t oa_pod_cap = 0; std::vector<int32_t> oa_rank; bool oa_rank_ok = false;
 };
 
 #define HIP_TRY(core, expr)                                                                                        \
@@ -584,6 +587,8 @@ int kai_core_destroy(kai_core* core) {
     if (core->dl_dev) { (void)hipFree(core->dl_dev); core->dl_dev = nullptr; }
     if (core->bn_pin) { (void)hipHostFree(core->bn_pin); core->bn_pin = nullptr; core->bn_pin_bytes = 0; }
     if (core->bn_dev) { (void)hipFree(core->bn_dev); core->bn_dev = nullptr; core->bn_dev_bytes = 0; }
+    if (core->oa_pin) { (void)hipHostFree(core->oa_pin); core->oa_pin = nullptr; core->oa_pin_bytes = 0; }
+    if (core->oa_dev) { (void)hipFree(core->oa_dev); core->oa_dev = nullptr; core->oa_dev_bytes = 0; core->oa_pod_cap = 0; }
     if (core->pin_buf) { (void)hipHostFree(core->pin_buf); core->pin_buf = nullptr; core->pin_bytes = 0; }
     if (core->up_pin) { (void)hipStreamSynchronize(core->stream); (void)hipHostFree(core->up_pin); core->up_pin = nullptr; core->up_pin_bytes = 0; }
     if (core->rccl_comm) { (void)hipStreamSynchronize(core->stream); if (RcclApi* a = rccl_api()) (void)a->CommDestroy(core->rccl_comm); core->rccl_comm = nullptr; }
@@ -684,7 +689,7 @@ static int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     core->legacy_on = any_legacy_mig; core->legacy_cnt.clear();
     if (any_legacy_mig) { core->legacy_cnt.assign((size_t)N, 0); for (int p = 0; p < P; p++)  // NodeInfo.LegacyMIGTasks (node_info.go:407-409): a node that holds a legacy MIG task takes no MIG request
         if ((s->pod_flags[p] & KAI_POD_LEGACY_MIG) && prep.pod_node[p] >= 0 && (s->pod_status[p] & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING))) { prep.node_flags[prep.pod_node[p]] |= KAI_NODE_LEGACY_MIG_I; core->legacy_cnt[(size_t)prep.pod_node[p]]++; } }
-    core->perm = prep.perm; core->bn_perm_ok = false;
+    core->perm = prep.perm; core->bn_perm_ok = false; core->oa_rank_ok = false;
 
     int rc;
 #define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
@@ -1332,6 +1337,21 @@ int kai_queue_shares(kai_core* core, kai_queue_share* out, int cap) {
     return KAI_OK;
 }
 
+// scratch of the victim search (and of kai_ops_apply's engine walk, which needs its second-residency table), kept for the rest of the session
+static int solver_ensure(kai_core* core) {
+    if (core->solver_ready) return KAI_OK;
+    KaiCtx& c = core->ctx;
+    char* base = nullptr; size_t bytes = solver_scratch_bytes(c.N, c.P, c.S, c.J, c.Q, c.W, c.D + c.T, c.TL, c.G);
+    int rc0 = dalloc(core, &base, bytes); if (rc0) return rc0;
+    HIP_TRY(core, hipMemsetAsync(base, 0, bytes, core->stream));
+    solver_scratch_bind(c.sv, base, c.N, c.P, c.S, c.J, c.Q, c.W, c.D + c.T, c.TL, c.G);
+    core->sv_base = base; core->sv_bytes = bytes;
+    HIP_TRY(core, hipMemsetAsync(c.sv.xr_key, 0xFF, sizeof(int64_t) * ((size_t)c.sv.xr_mask + 1), core->stream));  // empty residency table
+    { int32_t* xg = nullptr; int rcx = dalloc(core, &xg, (size_t)c.sv.xr_mask + 1); if (rcx) return rcx; c.sv.xr_group = xg; core->xr_base = (char*)xg; core->xr_bytes = ((size_t)c.sv.xr_mask + 1) * 4; }
+    core->solver_ready = true;
+    return KAI_OK;
+}
+
 int kai_action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_cap, int64_t* n_ops) {
     if (!core || !n_ops) return KAI_ERR_INVALID_ARG;
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
@@ -1342,16 +1362,7 @@ int kai_action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_
     const auto ta0 = std::chrono::steady_clock::now();
     auto ta_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     KaiCtx& c = core->ctx;
-    if (victim && !core->solver_ready) {  // scratch of the victim search, kept for the rest of the session
-        char* base = nullptr; size_t bytes = solver_scratch_bytes(c.N, c.P, c.S, c.J, c.Q, c.W, c.D + c.T, c.TL, c.G);
-        int rc0 = dalloc(core, &base, bytes); if (rc0) return rc0;
-        HIP_TRY(core, hipMemsetAsync(base, 0, bytes, core->stream));
-        solver_scratch_bind(c.sv, base, c.N, c.P, c.S, c.J, c.Q, c.W, c.D + c.T, c.TL, c.G);
-        core->sv_base = base; core->sv_bytes = bytes;
-        HIP_TRY(core, hipMemsetAsync(c.sv.xr_key, 0xFF, sizeof(int64_t) * ((size_t)c.sv.xr_mask + 1), core->stream));  // empty residency table
-        { int32_t* xg = nullptr; int rcx = dalloc(core, &xg, (size_t)c.sv.xr_mask + 1); if (rcx) return rcx; c.sv.xr_group = xg; core->xr_base = (char*)xg; core->xr_bytes = ((size_t)c.sv.xr_mask + 1) * 4; }
-        core->solver_ready = true;
-    }
+    if (victim) { int rc0 = solver_ensure(core); if (rc0) return rc0; }
     { int d = core->cfg.queue_depth[action]; c.queue_depth = d > 0 ? d : 0; c.action = action; }
     HIP_TRY(core, hipMemcpyAsync(core->d_ctx, &core->ctx, sizeof(KaiCtx), hipMemcpyHostToDevice, core->stream));
     // reset the per-action scalars, keep the proportion totals
@@ -1603,6 +1614,101 @@ int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_quer
     HIP_TRY(core, hipMemcpyAsync(h_out, d + L.out, (size_t)M * sizeof(kai_node_answer), hipMemcpyDeviceToHost, core->stream));
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     std::memcpy(out, h_out, (size_t)M * sizeof(kai_node_answer));
+    return KAI_OK;
+}
+
+int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_apply_result* result) {
+    // every host-decidable refusal before the first device call; `result` always leaves with a defined content
+    kai_apply_result res; res.first_bad = -1; res.path = KAI_APPLY_PATH_NONE; res.statements = 0;
+    if (result) *result = res;
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (n_ops < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_ops_apply: a negative count");
+    if (flags & ~(KAI_APPLY_CHECK_ONLY | KAI_APPLY_ENGINE_PATH)) return fail(core, KAI_ERR_INVALID_ARG, "kai_ops_apply: unknown flag bits");
+    if (n_ops > 0 && !ops) return fail(core, KAI_ERR_INVALID_ARG, "kai_ops_apply: ops is NULL");
+    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_ops_apply: a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (core->shared) return fail(core, KAI_ERR_UNSUPPORTED, "kai_ops_apply: a session with shared-GPU requests (kai_op carries no GPU group)");
+    if (n_ops == 0) return KAI_OK;
+    if (n_ops > (int64_t)0x7fffffff - 16) return fail(core, KAI_ERR_CAPACITY, "kai_ops_apply: more than 2^31 - 16 operations");
+    KaiCtx& c = core->ctx;
+    const int N = c.N, P = c.P, n = (int)n_ops;
+    bool non_alloc = false; int statements = 1;
+    for (int i = 0; i < n; i++) {  // O(n): what no device is needed for
+        const kai_op& o = ops[i];
+        const char* why = nullptr;
+        if (o.kind < KAI_OP_ALLOCATE || o.kind > KAI_OP_EVICT) why = "kai_ops_apply: kind outside 0..2";
+        else if (o.pod < 0 || o.pod >= P) why = "kai_ops_apply: pod index out of range";
+        else if (o.node < 0 || o.node >= N) why = "kai_ops_apply: node index out of range";
+        else if (o.pad != 0) why = "kai_ops_apply: pad is not zero";
+        else if (i > 0 && o.stmt < ops[i - 1].stmt) why = "kai_ops_apply: stmt decreases";
+        if (why) { if (result) result->first_bad = i; return fail(core, KAI_ERR_INVALID_ARG, why); }
+        if (o.kind != KAI_OP_ALLOCATE) non_alloc = true;
+        if (i > 0 && o.stmt != ops[i - 1].stmt) statements++;
+    }
+    res.statements = statements;
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
+    if ((size_t)P > core->oa_pod_cap || OaLayout(core->oa_pod_cap, n).end > core->oa_dev_bytes) {
+        if (core->oa_dev) (void)hipFree(core->oa_dev);
+        core->oa_dev = nullptr; core->oa_dev_bytes = 0;
+        const size_t pod_cap = std::max<size_t>((size_t)P + (size_t)P / 4, 1024);
+        const OaLayout G(std::max(pod_cap, core->oa_pod_cap), (int64_t)n + n / 2 + 1024);
+        HIP_TRY(core, hipMalloc(reinterpret_cast<void**>(&core->oa_dev), G.end));
+        core->oa_dev_bytes = G.end; core->oa_pod_cap = std::max(pod_cap, core->oa_pod_cap);
+        HIP_TRY(core, hipMemsetAsync(core->oa_dev, 0, G.head, core->stream));  // the per-pod arrays: zero between calls (the kernels clean what they touch)
+    }
+    const OaLayout L(core->oa_pod_cap, n);
+    const size_t up_bytes = L.end - L.head, pin_need = up_bytes + sizeof(OaHead);  // [head | ops][the verdict]
+    if (pin_need > core->oa_pin_bytes) {
+        if (core->oa_pin) (void)hipHostFree(core->oa_pin);
+        core->oa_pin = nullptr; core->oa_pin_bytes = 0;
+        const size_t want = std::max<size_t>(pin_need + pin_need / 2, (size_t)1 << 16);
+        HIP_TRY(core, hipHostMalloc(reinterpret_cast<void**>(&core->oa_pin), want, hipHostMallocDefault));
+        core->oa_pin_bytes = want;
+    }
+    if (!core->oa_rank_ok) { core->oa_rank.assign((size_t)std::max(N, 1), 0); for (int i = 0; i < N; i++) core->oa_rank[(size_t)core->perm[i]] = i; core->oa_rank_ok = true; }
+    // ---- one staging upload: [head | ops], the nodes as name ranks
+    unsigned char* h = core->oa_pin; unsigned char* d = core->oa_dev;
+    OaHead* hh = reinterpret_cast<OaHead*>(h); std::memset(hh, 0, sizeof(OaHead)); hh->bad = KAI_OA_NONE;
+    {   kai_op* dst = reinterpret_cast<kai_op*>(h + sizeof(OaHead)); const int32_t* rank = core->oa_rank.data();
+        parallel_chunks((size_t)n, [&](int, size_t i0, size_t i1) { for (size_t i = i0; i < i1; i++) { kai_op o = ops[i]; o.node = rank[o.node]; dst[i] = o; } }); }
+    HIP_TRY(core, hipMemcpyAsync(d + L.head, h, up_bytes, hipMemcpyHostToDevice, core->stream));
+    OaArgs a{};
+    a.n = n; a.flags = flags | (oa_wide_session(c) ? 0u : KAI_OA_NOT_WIDE); a.use_islot = oa_use_islot(c);
+    a.ops = (KAI_GP(const kai_op))(d + L.ops); a.head = (KAI_GP(OaHead))(d + L.head);
+    a.stamp = (KAI_GP(int32_t))(d + L.stamp); a.sh_status = (KAI_GP(int32_t))(d + L.sh_status); a.sh_node = (KAI_GP(int32_t))(d + L.sh_node);
+    // ---- the check and the chip-wide apply, one small download, one synchronise; the engine walk and a second download where the batch needs it (oa_drive)
+    struct Launcher {
+        kai_core* core; unsigned char* pin;
+        void check(int g, int b, const KaiCtx& c, const OaArgs& a) { hipLaunchKernelGGL(k_oa_check, dim3((unsigned)g), dim3((unsigned)b), 0, core->stream, c, a); }
+        void wide(int g, int b, const KaiCtx& c, const OaArgs& a) { hipLaunchKernelGGL(k_oa_wide, dim3((unsigned)g), dim3((unsigned)b), 0, core->stream, c, a); }
+        int engine(const KaiCtx&, const OaArgs& a) {
+            if (!(a.flags & KAI_APPLY_CHECK_ONLY)) { const int rcs = solver_ensure(core); if (rcs) return rcs; }  // (binds core->ctx.sv: the context is read after it)
+            hipLaunchKernelGGL(k_oa_engine, dim3(1), dim3(64), 0, core->stream, core->ctx, a);
+            return KAI_OK;
+        }
+        int read_head(OaHead& hv, const OaArgs& a) {
+            HIP_TRY(core, hipGetLastError());
+            HIP_TRY(core, hipMemcpyAsync(pin, (const void*)a.head, sizeof(OaHead), hipMemcpyDeviceToHost, core->stream));
+            HIP_TRY(core, hipStreamSynchronize(core->stream));
+            std::memcpy(&hv, pin, sizeof(OaHead));
+            return KAI_OK;
+        }
+    } launcher{core, h + up_bytes};
+    OaHead hv{}; int path = KAI_APPLY_PATH_NONE;
+    const int rcd = oa_drive(launcher, core->ctx, a, KAI_OA_WG, hv, path);
+    if (rcd == KAI_ERR_STATE) {
+        if (result) result->first_bad = hv.bad;
+        return fail(core, KAI_ERR_STATE, "kai_ops_apply: an operation's precondition fails (ALLOCATE: a Pending pod; PIPELINE: Pending or Releasing; EVICT: a pod on op.node)");
+    }
+    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[160]; std::snprintf(buf, sizeof buf, "kai_ops_apply: device engine fault code %d (engine source line %d), path %d reported %d", hv.fault, hv.fault_line, path, hv.applied); core->err = buf; return rcd; }
+    if (rcd) return rcd;
+    res.path = path;
+    if (!(flags & KAI_APPLY_CHECK_ONLY)) {
+        core->index_stale = true;           // neither path keeps the class index (sum1_key / sum1_node): rebuilt before the next action reads it
+        if (non_alloc) c.fast_ok = 0;       // something is releasing / pipelined in the session from here on, as after an action that committed such operations
+    }
+    if (result) *result = res;
     return KAI_OK;
 }
 

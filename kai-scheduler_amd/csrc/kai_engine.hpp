@@ -1317,17 +1317,17 @@ struct Engine {
         cx().st->ops_len = w;
         return true;
     }
-    KAI_HD void commit() {  // :536-575 — the cache side effects are replayed by the caller from out_ops
+    KAI_HD void commit(bool emit = true) {  // :536-575 — the cache side effects are replayed by the caller from out_ops; emit = false: operations that came FROM the caller (kai_ops_apply.hpp) are not handed back
         const int64_t len0 = el().h.out_len;
         for (int i = 0; i < cx().st->ops_len; i++) {
             if (!op_valid(i)) continue;
             StmtOp op = cx().ops[i]; if (op.name == OP_UNDO) continue;
-            if (el().h.out_len >= cx().out_cap) { fault(FAULT_OUT_CAP); break; }
+            if (emit && el().h.out_len >= cx().out_cap) { fault(FAULT_OUT_CAP); break; }
             kai_op o; o.seq = el().h.out_len; o.pod = op.pod; o.job = cx().p_job[op.pod]; o.node = cx().p_node[op.pod]; o.stmt = (int32_t)el().h.stmts; o.pad = 0;
             if (op.name == OP_EVICT) { o.kind = KAI_OP_EVICT; o.node = op.prev_node; cx().p_virtual[op.pod] = 0; cx().st->non_allocate_commits++; }
             else if (op.name == OP_PIPELINE) { o.kind = KAI_OP_PIPELINE; cx().st->non_allocate_commits++; }
             else { o.kind = KAI_OP_ALLOCATE; update_task_status(op.pod, KAI_POD_BINDING); }  // ssn.BindPod (framework/session.go:111-126)
-            cx().out_ops[el().h.out_len++] = o;
+            if (emit) cx().out_ops[el().h.out_len++] = o;
         }
         if (el().h.out_len > len0) el().h.stmts++;
         truncate_ops(0);

@@ -808,6 +808,61 @@ func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipe
 	return nodes, isPipeline, true
 }
 
+// AppliedOp is one operation a Go-run action committed through a live Statement: what ApplyOps hands to kai_ops_apply.  Stmt numbers the Statements in commit
+// order (non-decreasing along the slice); Node is the node of an Allocate / Pipeline, and the node the task is evicted from for an Evict.
+type AppliedOp struct {
+	Kind int32 // C.KAI_OP_ALLOCATE / KAI_OP_PIPELINE / KAI_OP_EVICT
+	Task *pod_info.PodInfo
+	Node *node_info.NodeInfo
+	Stmt int32
+}
+
+// ApplyOps: kai_ops_apply for a wrapper that runs ONE action in Go and wants the device back for the next one: the operations the Go action's Statements
+// committed go into the device session, which then is where the live session is.  It is NOT wired into action.Execute below, which still sets `fallback` for the
+// rest of the cycle on any non-zero status: a wrapper that calls it has to (1) collect what the Go action's Statements committed, in commit order, and (2) know that
+// the device wrote NOTHING for that action — true for a refusal made before the first launch (KAI_ERR_UNSUPPORTED for use_scheduling_signatures without job
+// signatures), not for KAI_ERR_CAPACITY or a device fault, after which the device session is somewhere inside the action and there is no undo.
+// false: no device session (or `fallback` already set), a task or node the snapshot does not know, or a refusal of kai_ops_apply (an operation whose precondition
+// fails against the device state: the two have parted) — `fallback` is set then.
+func ApplyOps(applied []AppliedOp) bool {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return false
+	}
+	pack := current.pack
+	if len(applied) == 0 {
+		return true
+	}
+	podOf := make(map[*pod_info.PodInfo]int, len(pack.pods))
+	for i, t := range pack.pods {
+		podOf[t] = i
+	}
+	nodeOf := make(map[*node_info.NodeInfo]int, len(pack.nodes))
+	for i, n := range pack.nodes {
+		nodeOf[n] = i
+	}
+	ops := make([]C.kai_op, len(applied))
+	for i, a := range applied {
+		p, knownPod := podOf[a.Task]
+		n, knownNode := nodeOf[a.Node]
+		if !knownPod || !knownNode {
+			pack.fallback = true
+			return false
+		}
+		ops[i].seq = C.int64_t(i)
+		ops[i].kind = C.int32_t(a.Kind)
+		ops[i].pod = C.int32_t(p)
+		ops[i].node = C.int32_t(n)
+		ops[i].job = -1
+		ops[i].stmt = C.int32_t(a.Stmt)
+	}
+	var res C.kai_apply_result
+	if rc := C.kai_ops_apply(core, &ops[0], C.int64_t(len(ops)), 0, &res); rc != 0 {
+		pack.fallback = true // the live session and the device state have parted: nothing more from the device in this cycle
+		return false
+	}
+	return true
+}
+
 // replay: the committed operations through the real Statement.  kai_op.stmt numbers the Statements of the action in
 // commit order; one id = one Statement, e.g. a reclaim "evict A, evict B, pipeline C" (framework/statement.go:536-575).
 // An operation the live session refuses (the cache moved on since the snapshot, a bind conflict) discards its whole Statement —
