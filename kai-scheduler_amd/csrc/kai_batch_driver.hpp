@@ -1,5 +1,5 @@
 // kai_batch_driver.hpp — host side of the batch path: buffers, qualification and the round loop (plan → fill → apply), written once against
-// a Launcher (kai_core.hip: HIP launches on the session's stream; tests/host_sim: the lock-step emulator of kai_simt.hpp).
+// a Launcher (kai_action.hpp DevLauncher: HIP launches on the session's stream; tests/host_sim: the lock-step emulator of kai_simt.hpp).
 //
 // Launcher interface:  void <kernel>(grid, block, args...)  for every kernel of kai_batch_kernels.hpp,
 //                      int read(void* host_dst, const void* dev_src, size_t bytes)   (synchronises),

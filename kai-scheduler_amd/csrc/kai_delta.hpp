@@ -31,6 +31,19 @@ struct DeltaView {
     const uint32_t* rank;  // [N] node_name_rank: caller's node index -> engine index
 };
 
+// Where the parts of one update lie in its staging buffer (the pinned and the device copy alike), every part on a 256-byte boundary: [pod | status | node | group | node |
+// flags] int32, [R][NNcap] doubles, the rows ([queue | priority | job] int32, then 8-byte values: deserved, limit, oqw, usage [3][NQ] each, the two min-runtimes [NQ] each,
+// last start [NJ]); behind what is sent, the gather's output [4][NP] int32 and its counters.
+struct DeltaLayout {
+    int NNcap;  // node entries: the delta's, and the nodes whose legacy-MIG bit a pod of the delta changes
+    size_t o_i32 = 0, o_f64, o_r32, o_r64, o_out, o_cnt, total;
+    static size_t up8(size_t b) { return (b + 255) & ~(size_t)255; }
+    DeltaLayout(int NP, int NN, int R, int NQ, int NJ, bool legacy_mig) : NNcap(NN + (legacy_mig ? 2 * NP : 0)) {
+        o_f64 = up8(((size_t)4 * NP + 2 * NNcap) * 4); o_r32 = up8(o_f64 + (size_t)R * NNcap * 8); o_r64 = up8(o_r32 + ((size_t)2 * NQ + NJ) * 4);
+        o_out = up8(o_r64 + ((size_t)14 * NQ + NJ) * 8); o_cnt = up8(o_out + (size_t)4 * NP * 4); total = o_cnt + 256;
+    }
+};
+
 __device__ __forceinline__ int kd_wave_sum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

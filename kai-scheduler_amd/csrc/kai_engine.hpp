@@ -50,10 +50,10 @@ template <class T> using kai_gptr = T*;
 
 namespace kai {
 
-// pod status groups: api/pod_status/pod_status.go:64-71
-KAI_HD bool st_active_used(int s) { return s & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING); }
-KAI_HD bool st_active_allocated(int s) { return s & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING); }
-KAI_HD bool st_alive(int s) { return s & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_PENDING | KAI_POD_GATED); }
+constexpr int32_t KAI_POD_ACTIVE = KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING;  // pod status groups: api/pod_status/pod_status.go:64-71 (this one: ActiveUsedStatus, a pod that holds resources on its node)
+KAI_HD bool st_active_used(int s) { return s & KAI_POD_ACTIVE; }
+KAI_HD bool st_active_allocated(int s) { return s & (KAI_POD_ACTIVE & ~KAI_POD_RELEASING); }
+KAI_HD bool st_alive(int s) { return s & ((KAI_POD_ACTIVE & ~KAI_POD_RELEASING) | KAI_POD_PENDING | KAI_POD_GATED); }
 KAI_HD bool st_allocated(int s) { return s & (KAI_POD_ALLOCATED | KAI_POD_BOUND | KAI_POD_BINDING | KAI_POD_RUNNING); }
 
 KAI_HD double kmin(double a, double b) { return a < b ? a : b; }  // math.Min / math.Max on finite, non-NaN operands

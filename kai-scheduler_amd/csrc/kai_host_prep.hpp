@@ -4,7 +4,7 @@
 // pods in TaskOrderFn order, the queue tree as CSR with a virtual root, each queue's jobs in their static order, queues by
 // depth, fair-share levels, the proportion plugin's per-queue quota records, and the scan classes (pods grouped by request
 // vector + predicate class) with the guards that admit a class to the device's class index.
-// Shared by kai_core.hip (uploads them to HBM) and by tests/host_sim (which debugs the engine's control flow without a GPU).
+// Shared by kai_session_open.hpp (uploads them to HBM) and by tests/host_sim (which debugs the engine's control flow without a GPU).
 #pragma once
 #include <algorithm>
 #include <chrono>

@@ -545,7 +545,7 @@ struct DevBackendT {
     __device__ static void mw_fetch_min32(int32_t* p, int32_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __device__ static double coh_f64(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __device__ static int32_t coh_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ static void grid_sync(MultiCtx* m, int clear) {  // the control lanes of the action's workgroups (all resident: one per compute unit at most, kai_core.hip)
+    __device__ static void grid_sync(MultiCtx* m, int clear) {  // the control lanes of the action's workgroups (all resident: one per compute unit at most, kai_action.hpp victim_setup)
         const int gen = __hip_atomic_load(&m->bar_gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __atomic_thread_fence(__ATOMIC_RELEASE);
         if (__hip_atomic_fetch_add(&m->bar_count, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == m->world) {

@@ -174,7 +174,7 @@ KAI_HD void oa_engine_walk(const KaiCtx& c, Backend& be, const OaArgs& a) {
     if (!st.fault) a.head->applied = KAI_APPLY_PATH_ENGINE;
 }
 
-// The call's control flow, written once against a Launcher (kai_core.hip: HIP launches on the session's stream; tests/host_sim/ops_apply_sim.cpp: the lock-step emulator):
+// The call's control flow, written once against a Launcher (kai_core.hip OaLauncher: HIP launches on the session's stream; tests/host_sim/ops_apply_sim.cpp: the lock-step emulator):
 //   void check(grid, lanes, c, a), void wide(grid, lanes, c, a), int engine(c, a), int read_head(OaHead&, a)  (synchronises).
 // KAI_OK: `path` took the batch (KAI_APPLY_CHECK_ONLY: would take it).  KAI_ERR_STATE: hv.bad is the first operation whose precondition fails; nothing was written.
 template <class L>

@@ -350,7 +350,7 @@ extern "C" int kai_hostsim_run(const kai_config* cfg, const kai_snapshot_soa* s,
     if (!sp.build(*cfg, s)) return KAI_ERR_UNSUPPORTED;
     const bool shared = sp.any;
     const int N = s->n_nodes, P = s->n_pods, S = s->n_podsets, J = s->n_jobs, Q = s->n_queues, R = s->n_res;
-    // lean_shared_pods_hold: kai_session_open (kai_core.hip) does not SEND the per-pod arrays of the shared-GPU model for a snapshot without shared-GPU requests and MIG rows — it
+    // lean_shared_pods_hold: kai_session_open (kai_session_open.hpp open_shared_gpus) does not SEND the per-pod arrays of the shared-GPU model for a snapshot without shared-GPU requests and MIG rows — it
     // writes the constants they hold on the device.  That they hold exactly those constants is checked here, on every snapshot the CPU suite runs.
     if (!sp.on) for (int p = 0; p < P; p++) {
         const double g = s->pod_req[(size_t)KAI_RES_GPU * P + p];
@@ -362,7 +362,7 @@ extern "C" int kai_hostsim_run(const kai_config* cfg, const kai_snapshot_soa* s,
     HostPrep prep; std::string err;
     prep.shared_pods = sp.any ? &sp : nullptr;
     if (prep.build(*cfg, s, err)) return KAI_ERR_INVALID_ARG;
-    {   // the other constants kai_session_open writes on the device instead of sending them (kai_core.hip: prep.groups_default, !prep.any_nominated) — checked on every snapshot the CPU suite runs
+    {   // the other constants kai_session_open writes on the device instead of sending them (kai_session_open.hpp: prep.groups_default, !prep.any_nominated) — checked on every snapshot the CPU suite runs
         bool ok = true;
         if (!prep.any_nominated) for (int p = 0; p < P; p++) ok = ok && prep.pod_nominated[p] == -1;
         if (prep.groups_default) {
@@ -627,7 +627,7 @@ extern "C" int kai_hostsim_run(const kai_config* cfg, const kai_snapshot_soa* s,
                 if (bs.buckets) index_stale = true;
                 g_sh_exchanges = bs.exchanges;
             } else {
-                // a node-sharded group shards the batch path's fill; every other action runs replicated on every rank (kai_core.hip kai_action_execute)
+                // a node-sharded group shards the batch path's fill; every other action runs replicated on every rank (kai_action.hpp action_engine)
                 if (g_sh_world > 1 && c.use_index) for (int b = 0; b < c.NB; b++) for (int k = 0; k < c.C; k++) HostBackend::build_block(c, k, b);  // the sharded fill left an index of the own slice only
                 eng.execute_allocate();
             }

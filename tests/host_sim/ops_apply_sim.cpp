@@ -74,7 +74,7 @@ void oasim_call(KaiCtx& c, const kai_op* src, int n) {
 void oasim_apply(KaiCtx& c) {
     OaSim& g = g_oa;
     g.n_ops_before = c.st->out_len; g.paths.clear();
-    if (g.at == 0) for (int q = 0; q < c.Q; q++) qnode_init(c, q, 0);  // k_qnode_static of the open (kai_core.hip launch_open_kernels): the host simulation fills the tree in its first action only, and the event handlers walk its parents
+    if (g.at == 0) for (int q = 0; q < c.Q; q++) qnode_init(c, q, 0);  // k_qnode_static of the open (kai_session_open.hpp launch_open_kernels): the host simulation fills the tree in its first action only, and the event handlers walk its parents
     for (int k = 0; k < g.n_calls; k++) {  // (a refused call ends the sequence: its status and result are what the caller sees)
         const int64_t lo = g.call_off ? g.call_off[k] : 0, hi = g.call_off ? g.call_off[k + 1] : g.n;
         oasim_call(c, g.ops + lo, (int)(hi - lo));

@@ -1,6 +1,6 @@
 """Spread placement on the GPU on the set-based fill kernels, on the MI355X through the C ABI: the cases of tests/test_fill_spread.py (same snapshots, same assertions) with
 the spread instantiations of k_fill_levels / k_fill_counts as they run on the device — against the oracle and, where the sets ran, against the general k_fill
-(KAI_FILL_GENERAL=1).  kai_core.hip reports the fill kernel in bits 60 - 62 of stats.reserved[1], the rounds in reserved[4]."""
+(KAI_FILL_GENERAL=1).  kai_action.hpp (action_stats) reports the fill kernel in bits 60 - 62 of stats.reserved[1], the rounds in reserved[4]."""
 import pytest
 
 import test_fill_spread as S

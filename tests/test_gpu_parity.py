@@ -450,7 +450,7 @@ def test_gpu_batch_random_regular(gpu, seed):
 
 
 def on_buckets(stats):
-    """the fill of the batch path ran on k_fill_buckets (sets of nodes by free devices in LDS; kai_core.hip puts bit 62 of reserved[1])"""
+    """the fill of the batch path ran on k_fill_buckets (sets of nodes by free devices in LDS; kai_action.hpp action_stats puts bit 62 of reserved[1])"""
     return bool((int(stats.reserved[1]) >> 62) & 1)
 
 

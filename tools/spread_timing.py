@@ -48,7 +48,7 @@ def run_child(idx, scale, steps, warmup, label, general, lib, prof=False):
     env = dict(os.environ)
     env.pop("KAI_FILL_GENERAL", None); env.pop("KAI_PROF", None)
     if prof:
-        env["KAI_PROF"] = "1"  # the library's own line per action on stderr: the fill's cycle clocks and command count (kai_core.hip)
+        env["KAI_PROF"] = "1"  # the library's own line per action on stderr: the fill's cycle clocks and command count (kai_action.hpp action_stats)
     if general:
         env["KAI_FILL_GENERAL"] = "1"
     code = CHILD.format(root=ROOT, lib=lib or "", idx=idx, scale=scale, steps=steps, warmup=warmup, label=label)
