@@ -526,6 +526,40 @@ int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_quer
 typedef struct kai_apply_result { int64_t first_bad; int32_t path; int32_t statements; } kai_apply_result;
 int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_apply_result* result /* may be NULL */);
 
+/* replaces: the stalegangeviction action (actions/stalegangeviction/stalegangeviction.go:29-90), the fifth of the default action list.  The decision is taken on
+ * the device against the session's CURRENT state (after whatever actions or kai_ops_apply calls ran) and the evictions are applied as kai_ops_apply applies
+ * KAI_OP_EVICT operations (ssn.Evict, framework/session.go:127-150).
+ * A job is stale (PodGroupInfo.IsStale, api/podgroup_info/job_info.go:417-432) when none of its pods is Succeeded, at least one is active-used (Allocated,
+ * Pipelined, Binding, Bound, Running, Releasing) and some pod-set has fewer active-used pods than its minAvailable.  The clock is the handle's
+ * (kai_core_set_now); it must be above 0, because 0 stands for "no timestamp" in job_stale_since_ns.
+ *  - job_stale_since_ns [n_jobs], in/out: StalenessInfo.TimeStamp, 0 = nil.  Afterwards: 0 for a job that is not stale, unchanged for a job that was stale
+ *    already, now for a newly stale job — also with a negative grace period (the reference stamps before it looks at the period).
+ *  - a stale job is evicted when now - since >= grace_ns (grace_ns < 0: never): job_stale_out[j] (may be NULL) is 1 exactly for those jobs (StalenessInfo.Stale),
+ *    also where no pod is left to evict (a job whose active pods are all Releasing); result->stale_jobs counts the stale jobs, result->expired_jobs the evicted.
+ *  - ops_out: one KAI_OP_EVICT per pod of an evicted job with an active-allocated status (the set above without Releasing), in ascending pod index (the
+ *    reference walks Go maps and fixes no order; this is the library's).  node: the caller's index of the pod's node; job: the pod's job; seq counts from 0;
+ *    stmt is one number per job, from 0 in array order — a job's pods are contiguous, so the length of its run of equal stmt is its EvictionGangSize; pad 0.
+ *    The array can be passed to kai_ops_apply of another handle as it is.
+ * After KAI_OK without KAI_STALE_DRY_RUN the handle is indistinguishable from a twin in the same state on which kai_ops_apply(ops_out, *n_ops) ran:
+ * kai_pod_states, kai_node_states and kai_queue_shares bit for bit, the answers of kai_best_node(s), every later action.  kai_session_reset and
+ * kai_session_update* discard the evictions as they discard action results; kai_action_stats_get is unaffected.  With KAI_STALE_DRY_RUN the session stays
+ * bit for bit as it was and everything is reported the same way; result->path (KAI_APPLY_PATH_*) then says which apply path would run.  Nothing to evict:
+ * KAI_OK, *n_ops = 0, the timestamps are updated, no apply launch.
+ * Refusals, all decided before the first write to the session and to the caller's arrays:
+ *  - KAI_ERR_INVALID_ARG: a wrong version, unknown flag bits, NULL params / job_stale_since_ns / n_ops, NULL ops_out with ops_cap > 0, a negative capacity,
+ *    a negative job_stale_since_ns entry, a clock that is not above 0;
+ *  - KAI_ERR_STATE: no open session;
+ *  - KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1); a session with shared-GPU requests — kai_ops_apply's restriction (kai_op carries no GPU
+ *    group), not lifted here;
+ *  - KAI_ERR_CAPACITY: ops_cap is below the number of evictions; *n_ops holds the number needed (n_pods always suffices). */
+#define KAI_STALE_VERSION 1u
+#define KAI_STALE_DRY_RUN 0x1u   /* decide and report; the session is not written */
+typedef struct kai_stale_params { uint32_t version; uint32_t flags; int64_t grace_ns; /* < 0: never evict */ } kai_stale_params;
+typedef struct kai_stale_result { int32_t stale_jobs; int32_t expired_jobs; int64_t n_ops; int32_t path; int32_t pad; } kai_stale_result;
+int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params,
+                            int64_t* job_stale_since_ns /* [n_jobs] in/out, 0 = nil */, uint8_t* job_stale_out /* [n_jobs] or NULL: StalenessInfo.Stale */,
+                            kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, kai_stale_result* result /* may be NULL */);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

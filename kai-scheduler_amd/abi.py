@@ -236,6 +236,19 @@ class KaiApplyResult(C.Structure):
     _fields_ = [("first_bad", C.c_int64), ("path", C.c_int32), ("statements", C.c_int32)]
 
 
+STALE_VERSION, STALE_DRY_RUN = 1, 0x1  # KAI_STALE_VERSION, KAI_STALE_DRY_RUN
+
+
+class KaiStaleParams(C.Structure):
+    """kai_stale_params (include/kai_core.h): kai_stale_gang_eviction's grace period (negative: never evict) and flags."""
+    _fields_ = [("version", C.c_uint32), ("flags", C.c_uint32), ("grace_ns", C.c_int64)]
+
+
+class KaiStaleResult(C.Structure):
+    """kai_stale_result (include/kai_core.h): the stale jobs, those whose grace period ran out, the evictions, the apply path (APPLY_PATH_*) that took them."""
+    _fields_ = [("stale_jobs", C.c_int32), ("expired_jobs", C.c_int32), ("n_ops", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

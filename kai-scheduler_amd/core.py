@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ops_apply",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ops_apply", "kai_stale_gang_eviction",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -125,6 +125,8 @@ def load_library(path: str = LIB_PATH):
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
     lib.kai_best_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiNodeAnswer)]
     lib.kai_ops_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiApplyResult)]
+    lib.kai_stale_gang_eviction.argtypes = [C.c_void_p, C.POINTER(abi.KaiStaleParams), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(abi.KaiOp), C.c_int64,
+                                            C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -339,6 +341,22 @@ class Session:
             err.result = res
             raise err
         return res
+
+    def stale_gang_eviction(self, stale_since, grace_ns: int, dry_run: bool = False):
+        """kai_stale_gang_eviction: the stalegangeviction action against the session's current state, at the handle's clock (KaiCore.set_now).  stale_since: per job
+        StalenessInfo.TimeStamp in ns, 0 = nil (not modified); grace_ns < 0: never evict; dry_run: decide and report, the session is not written.
+        Returns (ops, stale_since, stale, result): the evictions as kai_op records in ascending pod index, the new timestamps, StalenessInfo.Stale per job as a bool
+        array, and the kai_stale_result."""
+        J, P = self.snap.n_jobs, self.snap.n_pods
+        since = np.zeros(max(J, 1), np.int64)
+        since[:J] = np.asarray(stale_since, dtype=np.int64).ravel()
+        stale = np.zeros(max(J, 1), np.uint8)
+        ops = np.zeros(max(P, 1), _OP_DTYPE)
+        n, res = C.c_int64(0), abi.KaiStaleResult()
+        params = abi.KaiStaleParams(abi.STALE_VERSION, abi.STALE_DRY_RUN if dry_run else 0, int(grace_ns))
+        self.core._check(self.core.lib.kai_stale_gang_eviction(self.core.handle, C.byref(params), since.ctypes.data_as(C.POINTER(C.c_int64)), stale.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                               ops.ctypes.data_as(C.POINTER(abi.KaiOp)), P, C.byref(n), C.byref(res)))
+        return ops[:n.value].copy(), since[:J], stale[:J].astype(bool), res
 
     def gpu_groups(self):
         """PodInfo.GPUGroups[0] of the active fraction pods (-1 elsewhere): kai_pod_gpu_groups."""

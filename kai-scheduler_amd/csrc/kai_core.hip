@@ -229,6 +229,17 @@ struct OaLauncher {
     }
 };
 
+// kai_ops_apply's device scratch for n operations of the open session (OaLayout(core->oa_pod_cap, n) afterwards): grows on demand, no allocation once the handle is warm
+static int oa_reserve_scratch(kai_core* core, int n) {
+    const int P = core->ctx.P;
+    const size_t pod_cap = std::max(std::max<size_t>((size_t)P + (size_t)P / 4, 1024), core->oa_pod_cap);
+    const OaLayout G(pod_cap, (int64_t)n + n / 2 + 1024);  // the enlarged capacities: what a growth allocates
+    bool grew = false;  // (per-pod arrays that no longer hold the session's pods force the growth whatever the bytes)
+    KAI_TRY(reserve(core, core->oa_dev, (size_t)P > core->oa_pod_cap ? SIZE_MAX : OaLayout(core->oa_pod_cap, n).end, G.end, &grew));
+    if (grew) { core->oa_pod_cap = pod_cap; HIP_TRY(core, hipMemsetAsync(core->oa_dev.p, 0, G.head, core->stream)); }  // the per-pod arrays: zero between calls (the kernels clean what they touch)
+    return KAI_OK;
+}
+
 int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_apply_result* result) {
     // every host-decidable refusal before the first device call; `result` always leaves with a defined content
     kai_apply_result res; res.first_bad = -1; res.path = KAI_APPLY_PATH_NONE; res.statements = 0;
@@ -260,11 +271,7 @@ int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t fla
     res.statements = statements;
     HIP_TRY(core, hipSetDevice(core->device));
     // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
-    const size_t pod_cap = std::max(std::max<size_t>((size_t)P + (size_t)P / 4, 1024), core->oa_pod_cap);
-    const OaLayout G(pod_cap, (int64_t)n + n / 2 + 1024);  // the enlarged capacities: what a growth allocates
-    bool grew = false;  // (per-pod arrays that no longer hold the session's pods force the growth whatever the bytes)
-    KAI_TRY(reserve(core, core->oa_dev, (size_t)P > core->oa_pod_cap ? SIZE_MAX : OaLayout(core->oa_pod_cap, n).end, G.end, &grew));
-    if (grew) { core->oa_pod_cap = pod_cap; HIP_TRY(core, hipMemsetAsync(core->oa_dev.p, 0, G.head, core->stream)); }  // the per-pod arrays: zero between calls (the kernels clean what they touch)
+    KAI_TRY(oa_reserve_scratch(core, n));
     const OaLayout L(core->oa_pod_cap, n);
     const size_t up_bytes = L.end - L.head, pin_need = up_bytes + sizeof(OaHead);  // [head | ops][the verdict]
     KAI_TRY(reserve(core, core->oa_pin, pin_need, std::max<size_t>(pin_need + pin_need / 2, (size_t)1 << 16)));
@@ -295,6 +302,101 @@ int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t fla
         if (non_alloc) c.fast_ok = 0;       // something is releasing / pipelined in the session from here on, as after an action that committed such operations
     }
     if (result) *result = res;
+    return KAI_OK;
+}
+
+// kai_stale_gang_eviction's kernels for sg_drive (kai_stale_gangs.hpp), on top of the apply's launcher; pin: [the counts | the apply's verdict] in the handle's staging
+struct SgLauncher : OaLauncher {
+    unsigned char* pin_counts;
+    SgLauncher(kai_core* core_, unsigned char* pin_) : OaLauncher{core_, pin_ + sizeof(SgHead)}, pin_counts(pin_) {}
+    static dim3 g(int n) { return dim3((unsigned)n); }
+    void succeeded(int n, int b, const KaiCtx& c, const SgArgs& a) { hipLaunchKernelGGL(k_sg_succeeded, g(n), g(b), 0, core->stream, c, a); }
+    void jobs(int n, int b, const KaiCtx& c, const SgArgs& a) { hipLaunchKernelGGL(k_sg_jobs, g(n), g(b), 0, core->stream, c, a); }
+    void first(int n, int b, const KaiCtx& c, const SgArgs& a) { hipLaunchKernelGGL(k_sg_first, g(n), g(b), 0, core->stream, c, a); }
+    void totals(int n, int b, const KaiCtx& c, const SgArgs& a) { hipLaunchKernelGGL(k_sg_totals, g(n), g(b), 0, core->stream, c, a); }
+    void scan(int b, const SgArgs& a) { hipLaunchKernelGGL(k_sg_scan, g(1), g(b), 0, core->stream, a); }
+    void emit(int n, int b, const KaiCtx& c, const SgArgs& a) { hipLaunchKernelGGL(k_sg_emit, g(n), g(b), 0, core->stream, c, a); }
+    int read_counts(SgHead& hd, const SgArgs& a) {
+        HIP_TRY(core, hipGetLastError());
+        HIP_TRY(core, hipMemcpyAsync(pin_counts, (const void*)a.head, sizeof(SgHead), hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+        std::memcpy(&hd, pin_counts, sizeof(SgHead));
+        return KAI_OK;
+    }
+    int reserve_ops(int n, SgArgs& a, OaArgs& oa) {
+        KAI_TRY(oa_reserve_scratch(core, n));
+        const OaLayout L(core->oa_pod_cap, n); unsigned char* d = core->oa_dev.p;
+        a.oa_head = (KAI_GP(OaHead))(d + L.head); a.ops = (KAI_GP(kai_op))(d + L.ops);
+        oa.ops = (KAI_GP(const kai_op))(d + L.ops); oa.head = (KAI_GP(OaHead))(d + L.head);
+        oa.stamp = (KAI_GP(int32_t))(d + L.stamp); oa.sh_status = (KAI_GP(int32_t))(d + L.sh_status); oa.sh_node = (KAI_GP(int32_t))(d + L.sh_node);
+        return KAI_OK;
+    }
+};
+
+int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params, int64_t* job_stale_since_ns, uint8_t* job_stale_out,
+                            kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, kai_stale_result* result) {
+    // every host-decidable refusal before the first device call and before the first write to the caller's arrays
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (!params || !job_stale_since_ns || !n_ops) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: params / job_stale_since_ns / n_ops is NULL");
+    if (params->version != KAI_STALE_VERSION) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: wrong params version");
+    if (params->flags & ~KAI_STALE_DRY_RUN) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: unknown flag bits");
+    if (ops_cap < 0 || (ops_cap > 0 && !ops_out)) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: a negative capacity, or ops_out is NULL");
+    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_stale_gang_eviction: a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (core->shared) return fail(core, KAI_ERR_UNSUPPORTED, "kai_stale_gang_eviction: a session with shared-GPU requests (kai_op carries no GPU group)");
+    KaiCtx& c = core->ctx;
+    if (c.now_ns <= 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: the handle's clock is not above 0 (kai_core_set_now): 0 stands for no timestamp");
+    const int J = c.J, P = c.P;
+    for (int j = 0; j < J; j++) if (job_stale_since_ns[j] < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: a negative job_stale_since_ns entry");
+    const bool dry_run = (params->flags & KAI_STALE_DRY_RUN) != 0;
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
+    const int n_wgs = (int)(((int64_t)P + KAI_SG_WG - 1) / KAI_SG_WG);
+    if ((size_t)J > core->sg_job_cap || (size_t)n_wgs > core->sg_wg_cap) {
+        const size_t job_cap = std::max(std::max<size_t>((size_t)J + (size_t)J / 4, 1024), core->sg_job_cap), wg_cap = std::max(std::max<size_t>((size_t)n_wgs + (size_t)n_wgs / 4, 64), core->sg_wg_cap);
+        const SgLayout G(job_cap, wg_cap);
+        KAI_TRY(reserve(core, core->sg_dev, SIZE_MAX, G.end));
+        core->sg_job_cap = job_cap; core->sg_wg_cap = wg_cap;
+        HIP_TRY(core, hipMemsetAsync(core->sg_dev.p, 0, G.end, core->stream));  // the Succeeded flags: zero between calls (k_sg_jobs clears what it reads)
+    }
+    const SgLayout L(core->sg_job_cap, core->sg_wg_cap);
+    // staging: [counts | timestamps] up; [counts | the apply's verdict | timestamps | Stale bytes | operations] down
+    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t up_bytes = sizeof(SgHead) + (size_t)J * 8, dn_since = al(up_bytes) + sizeof(SgHead) + sizeof(OaHead), dn_stale = dn_since + (size_t)J * 8, dn_ops = al(dn_stale + (size_t)J);
+    KAI_TRY(reserve(core, core->sg_pin, dn_ops, std::max<size_t>(dn_ops + dn_ops / 2, (size_t)1 << 16)));
+    unsigned char* h = core->sg_pin.p; unsigned char* d = core->sg_dev.p;
+    // ---- one upload: the zeroed counts and the caller's timestamps
+    std::memset(h, 0, sizeof(SgHead));
+    std::memcpy(h + sizeof(SgHead), job_stale_since_ns, (size_t)J * 8);
+    HIP_TRY(core, hipMemcpyAsync(d + L.head, h, up_bytes, hipMemcpyHostToDevice, core->stream));
+    SgArgs a{};
+    a.now_ns = c.now_ns; a.grace_ns = params->grace_ns; a.n_wgs = n_wgs;
+    a.head = (KAI_GP(SgHead))(d + L.head); a.since = (KAI_GP(int64_t))(d + L.since); a.expired = (KAI_GP(uint8_t))(d + L.expired);
+    a.succ = (KAI_GP(int32_t))(d + L.succ); a.first = (KAI_GP(int32_t))(d + L.first); a.wg_e = (KAI_GP(int32_t))(d + L.wg_e); a.wg_f = (KAI_GP(int32_t))(d + L.wg_f);
+    // ---- the decision, one small download, the apply (sg_drive)
+    SgLauncher launcher(core, h + al(up_bytes));
+    SgHead hd{}; OaHead hv{}; int path = KAI_APPLY_PATH_NONE;
+    const int rcd = sg_drive(launcher, core->ctx, a, KAI_SG_WG, dry_run, ops_cap, hd, hv, path);
+    if (rcd == KAI_ERR_CAPACITY) { *n_ops = hd.n_ops; return fail(core, KAI_ERR_CAPACITY, "kai_stale_gang_eviction: ops_cap is below the number of evictions (*n_ops holds it)"); }
+    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[200]; std::snprintf(buf, sizeof buf, "kai_stale_gang_eviction: the apply refused the evictions (first bad %d, device engine fault code %d, engine source line %d)", hv.bad, hv.fault, hv.fault_line); core->err = buf; return rcd; }
+    if (rcd) return rcd;
+    const int n = hd.n_ops;
+    if (n > 0 && !dry_run) { core->index_stale = true; c.fast_ok = 0; }  // as kai_ops_apply leaves the handle after evictions
+    // ---- the timestamps, the Stale bytes and the operations down
+    KAI_TRY(reserve(core, core->sg_pin, dn_ops + (size_t)n * sizeof(kai_op), dn_ops + ((size_t)n + (size_t)n / 2 + 1024) * sizeof(kai_op)));
+    h = core->sg_pin.p;
+    if (J) {
+        HIP_TRY(core, hipMemcpyAsync(h + dn_since, d + L.since, (size_t)J * 8, hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipMemcpyAsync(h + dn_stale, d + L.expired, (size_t)J, hipMemcpyDeviceToHost, core->stream));
+    }
+    if (n) HIP_TRY(core, hipMemcpyAsync(h + dn_ops, (const void*)a.ops, (size_t)n * sizeof(kai_op), hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    std::memcpy(job_stale_since_ns, h + dn_since, (size_t)J * 8);
+    if (job_stale_out) std::memcpy(job_stale_out, h + dn_stale, (size_t)J);
+    {   const kai_op* src = reinterpret_cast<const kai_op*>(h + dn_ops); const int32_t* perm = core->perm.data();  // name rank -> the caller's node index
+        parallel_chunks((size_t)n, [&](int, size_t i0, size_t i1) { for (size_t i = i0; i < i1; i++) { kai_op o = src[i]; o.node = perm[o.node]; ops_out[i] = o; } }); }
+    *n_ops = n;
+    if (result) { result->stale_jobs = hd.stale_jobs; result->expired_jobs = hd.expired_jobs; result->n_ops = n; result->path = path; result->pad = 0; }
     return KAI_OK;
 }
 

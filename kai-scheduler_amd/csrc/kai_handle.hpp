@@ -23,6 +23,7 @@
 #include "kai_delta.hpp"
 #include "kai_best_nodes.hpp"
 #include "kai_ops_apply.hpp"
+#include "kai_stale_gangs.hpp"
 
 using namespace kai;
 
@@ -107,7 +108,9 @@ struct kai_core {
     HandleBuf bn_pin{true}, bn_dev{false}; bool bn_perm_ok = false; int cus = 0;  // (compute units of the device: device_cus)
     // kai_ops_apply (kai_ops_apply.hpp): pinned staging and device scratch, grow, live with the handle; pods the scratch's per-pod arrays hold; caller's node index -> name rank (of this session's permutation)
     HandleBuf oa_pin{true}, oa_dev{false}; size_t oa_pod_cap = 0; std::vector<int32_t> oa_rank; bool oa_rank_ok = false;
-    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
+    // kai_stale_gang_eviction (kai_stale_gangs.hpp): pinned staging and device scratch, grow, live with the handle; jobs and pod-grid workgroups the scratch's arrays hold
+    HandleBuf sg_pin{true}, sg_dev{false}; size_t sg_job_cap = 0, sg_wg_cap = 0;
+    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
 };
 
 // leave the function with a step's status unless it is KAI_OK; a HIP call's error becomes KAI_ERR_HIP with the call's text in kai_last_error

@@ -34,6 +34,7 @@ import (
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/actions/preempt"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/actions/reclaim"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/actions/utils"
+	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api/common_info"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api/eviction_info"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api/node_info"
@@ -859,6 +860,75 @@ func ApplyOps(applied []AppliedOp) bool {
 	if rc := C.kai_ops_apply(core, &ops[0], C.int64_t(len(ops)), 0, &res); rc != 0 {
 		pack.fallback = true // the live session and the device state have parted: nothing more from the device in this cycle
 		return false
+	}
+	return true
+}
+
+// StaleGangEviction: the stalegangeviction action (actions/stalegangeviction/stalegangeviction.go:29-90) decided by the device against ITS session state — where
+// the placement actions of this cycle left it — in ONE kai_stale_gang_eviction call.  StalenessInfo.TimeStamp of every job goes down as nanoseconds (0 = nil), the
+// clock is the handle's (kai_core_set_now; OnSessionOpen sets it from Now), gracePeriod is ssn.GetGlobalDefaultStalenessGracePeriod() (negative: never evict).
+// What comes back is replayed into the live session: each run of equal kai_op.stmt is one job's gang, evicted task by task through ssn.Evict (which is
+// ssn.Cache.Evict plus the session's own bookkeeping, framework/session.go:127-150) with EvictionGangSize = the run's length and Action = StaleGangEviction, as the
+// reference does without a Statement; then TimeStamp / Stale are written back to every job.  The device keeps nanoseconds; the annotation the status updater
+// writes from TimeStamp keeps seconds (RFC 3339, cache/status_updater/default_status_updater.go:446-456), so a stamp read back from the pod group in the next
+// cycle is up to a second older than the one set here — the same truncation the Go action lives with.
+// An eviction the live session refuses is logged by the reference and skipped; here it also sets `fallback`, because the device has evicted the task.
+// false: no device session (or `fallback` already set), or a refusal of the entry point (shared-GPU requests, a clock that is not above 0): nothing was written,
+// the caller runs the Go action instead.
+func StaleGangEviction(ssn *framework.Session, gracePeriod time.Duration) bool {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return false
+	}
+	pack := current.pack
+	if len(pack.jobs) == 0 {
+		return true
+	}
+	since := make([]C.int64_t, len(pack.jobs))
+	for j, job := range pack.jobs {
+		if job.StalenessInfo.TimeStamp != nil {
+			since[j] = C.int64_t(job.StalenessInfo.TimeStamp.UnixNano())
+		}
+	}
+	stale := make([]C.uint8_t, len(pack.jobs))
+	capOps := len(pack.pods) // always suffices
+	ops := make([]C.kai_op, capOps+1)
+	params := C.kai_stale_params{version: C.KAI_STALE_VERSION, grace_ns: C.int64_t(gracePeriod.Nanoseconds())}
+	var n C.int64_t
+	var res C.kai_stale_result
+	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+	if rc := C.kai_stale_gang_eviction(core, &params, &since[0], &stale[0], &ops[0], C.int64_t(capOps), &n, &res); rc != 0 {
+		return false // decided before the first write: the device session and the caller's arrays are as they were
+	}
+	ok := true
+	for i := 0; i < int(n); {
+		id, first := ops[i].stmt, i
+		for i < int(n) && ops[i].stmt == id {
+			i++
+		}
+		job := pack.jobs[ops[first].job]
+		meta := eviction_info.EvictionMetadata{EvictionGangSize: i - first, Action: string(framework.StaleGangEviction)}
+		for k := first; k < i; k++ {
+			task := pack.pods[ops[k].pod]
+			if err := ssn.Evict(task, api.GetGangEvictionMessage(task, job), meta); err != nil {
+				ok = false // the live session and the device state have parted: nothing more from the device in this cycle
+			}
+		}
+	}
+	for j, job := range pack.jobs {
+		if since[j] == 0 {
+			job.StalenessInfo.TimeStamp, job.StalenessInfo.Stale = nil, false
+			continue
+		}
+		if job.StalenessInfo.TimeStamp == nil || job.StalenessInfo.TimeStamp.UnixNano() != int64(since[j]) {
+			t := time.Unix(0, int64(since[j]))
+			job.StalenessInfo.TimeStamp = &t
+		}
+		if stale[j] != 0 {
+			job.StalenessInfo.Stale = true
+		}
+	}
+	if !ok {
+		pack.fallback = true
 	}
 	return true
 }

@@ -32,7 +32,11 @@ var zeroDepth = map[C.int]bool{}
 var actionIndex = map[string]int{"allocate": C.KAI_ACTION_ALLOCATE, "consolidation": C.KAI_ACTION_CONSOLIDATION, "reclaim": C.KAI_ACTION_RECLAIM, "preempt": C.KAI_ACTION_PREEMPT}
 
 // ConfigFromScheduler fills kai_config from the scheduler's configuration.  Returns the actions of conf.Actions that the device path implements, in order
-// (stalegangeviction is not a placement action and stays on the Go side).
+// (stalegangeviction is no kai_action_execute action and is not in that list; the device takes it through its own entry point, independent of KAI_ACTION_*:
+// a wrapper that wants the whole default cycle on the handle registers, beside the four actions of kai_cgo.go's init(),
+//     framework.RegisterAction(&staleAction{goAction: stalegangeviction.New()})
+// whose Execute is `if !gpucore.StaleGangEviction(ssn, ssn.GetGlobalDefaultStalenessGracePeriod()) { goAction.Execute(ssn) }` and whose Name is
+// framework.StaleGangEviction — last in the default list, so it sees the device session where allocate .. preempt left it).
 func ConfigFromScheduler(sc *conf.SchedulerConfiguration, params conf.SchedulerParams, now time.Time) (C.kai_config, []string) {
 	var cfg C.kai_config
 	cfg.abi_version = C.KAI_ABI_VERSION

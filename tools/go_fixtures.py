@@ -62,6 +62,9 @@ SOURCES = [
     ("actions/integration_tests/preempt/preemptMIG_test.go", ["allocate", "consolidation", "reclaim", "preempt", "stalegangeviction"]),
     ("actions/integration_tests/reclaim/reclaimFractional_test.go", ["allocate", "consolidation", "reclaim", "preempt", "stalegangeviction"]),
     ("actions/integration_tests/reclaim/reclaimMIG_test.go", ["allocate", "consolidation", "reclaim", "preempt", "stalegangeviction"]),
+    # the action's own table: the session runs under OverrideGlobalDefaultStalenessGracePeriod(60 * time.Second) (stalegangeviction_test.go:208); a job's StaleDuration is how
+    # long ago its staleness timestamp was set (test_utils/jobs_fake/jobs.go)
+    ("actions/stalegangeviction/stalegangeviction_test.go", ["stalegangeviction"], {"staleness_grace_period_ns": 60 * 1_000_000_000}),
 ]
 
 
@@ -459,7 +462,7 @@ def extract(path: str):
 def main():
     os.makedirs(OUT, exist_ok=True)
     summary = {}
-    for rel, actions in SOURCES:
+    for rel, actions, *extra in SOURCES:
         path = os.path.join(REF, rel)
         if not os.path.exists(path):
             print("missing", rel); continue
@@ -468,6 +471,8 @@ def main():
         good = [c for c in cases if "_error" not in c]
         name = rel.replace("actions/", "").replace("/", "__").replace("_test.go", "")
         doc = {"source": f"pkg/scheduler/{rel}", "actions": actions, "cases": good, "parse_errors": errs}
+        for more in extra:  # what the test function sets outside its table
+            doc.update(more)
         with open(os.path.join(OUT, name + ".json"), "w") as f:
             json.dump(doc, f, indent=1, sort_keys=True)
         summary[name] = (len(good), len(errs))
