@@ -14,7 +14,7 @@ constexpr int KB_INF = 0x7fffffff;
 #define KB_ACC(slot, t0)
 #endif
 constexpr int KB_APPLY_INNER = 1024;  // inner queue nodes whose shares k_apply_jobs sums per workgroup in LDS (48 KB); the nodes beyond take the atomics directly
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(KAI_EMU_DEVICE_SIZES)  // (KAI_EMU_DEVICE_SIZES: the emulator at the device's sizes, tests/test_batch_device_sizes.py)
 constexpr int KB_PLAN_SCAN_THREADS = 1024; // workgroup of k_plan_scan (a multiple of 64, at most 1024): the scan is latency bound (f64 divisions of the keys), more wavefronts hide more of it
 constexpr int KB_PLAN_SCAN_ELEMS = 4;      // positions of a stream per thread and step
 constexpr int KB_PLAN_SETUP_THREADS = 1024; // the one workgroup of k_plan_setup (passes over the Q + 1 queue nodes: config 5's 2 185 in 3 steps instead of 9)

@@ -33,7 +33,7 @@ struct RoundCtl {
 };
 
 // k_plan_scan cut into segments (kai_plan_segments.hpp): a workgroup of KPS_T threads takes KPS_SEG consecutive positions of a node's stream, KPS_E per thread
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(KAI_EMU_DEVICE_SIZES)  // (KAI_EMU_DEVICE_SIZES: the emulator at the device's sizes, tests/test_batch_device_sizes.py)
 enum { KPS_T = 256, KPS_E = 4 };
 #else
 enum { KPS_T = 64, KPS_E = 2 };  // the emulator: short segments, so that the tests' small clusters cut their streams into several

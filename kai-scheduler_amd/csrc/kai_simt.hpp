@@ -181,21 +181,25 @@ inline void launch(int grid, int block, size_t dyn_lds_bytes, const std::functio
         int live = block;
         // KW_EMU_ORDER: how the waves of a workgroup take turns between their collectives — unset / 0: in order; 1: in reverse; 2: every wave sits
         // out a pass with probability 1/2 (seeded), so the waves drift apart as far as the barriers allow.  Races between waves show up as
-        // results that depend on this setting.
+        // results that depend on this setting.  3: one wave at a time, the last one first, runs as far as it can get (to a workgroup barrier or its end) before any other
+        // wave moves — the schedule that shows a missing barrier between two uses of the same LDS, which 0 .. 2 do not: there the waves stay within a collective or a few
+        // of each other (tests/test_kw_conformance.py).  Not for kernels whose wavefronts poll each other (relax()): the polling wave would run alone for ever.
         static const int order = [] { const char* v = std::getenv("KW_EMU_ORDER"); return v ? std::atoi(v) : 0; }();
         static uint64_t rng = [] { const char* v = std::getenv("KW_EMU_SEED"); return 0x9e3779b97f4a7c15ull + (v ? (uint64_t)std::atoll(v) * 0x100000001b3ull : 0); }();
         while (live > 0) {
             bool progress = false;
             const int nwv = (block + 63) / 64;
             for (int wi = 0; wi < nwv; wi++) {
-                const int w = order == 1 ? nwv - 1 - wi : wi;
+                const int w = (order == 1 || order == 3) ? nwv - 1 - wi : wi;
                 if (order == 2) { rng = rng * 6364136223846793005ull + 1442695040888963407ull; if ((rng >> 40) & 1) continue; }
+                bool ran = false;
                 for (int t = w * 64; t < block && t < w * 64 + 64; t++) {
                     if (e.fibers[t].state != F_RUN) continue;
                     e.cur = t; kw_switch_ctx(&e.sched_sp, e.fibers[t].sp);
-                    progress = true;
+                    progress = ran = true;
                     if (e.fibers[t].state == F_DONE) live--;
                 }
+                if (order == 3 && ran) break;  // (its wave collectives are released below; the next pass starts with this wave again)
             }
             if (order == 2 && !progress) { bool any = false; for (int t = 0; t < block; t++) if (e.fibers[t].state == F_RUN) any = true; if (any) continue; }  // every wave sat out
             // release the barriers every live participant has reached
@@ -292,7 +296,11 @@ KW_DEV void wave_argmax_first(uint64_t& key, int& n) {
     n = shfl(n, l);
     key = m;
 }
-// inclusive prefix sums over the 64 lanes (Hillis-Steele with shfl_up)
+// inclusive prefix sums over the 64 lanes (Hillis-Steele with shfl_up).  Contract (tests/kw_conformance_cases.py): lane l returns v[0] + .. + v[l] of its wavefront's live
+// lanes, in some order of addition; int sums do not overflow; a double sum that is zero comes back as a zero of EITHER sign (on the device a step without a source adds +0.0,
+// which turns a lane's sum of −0.0s into +0.0 — lane 0, not lane 63; the shuffle form leaves −0.0 everywhere).
+// kw::shfl(v, src) reads lane src & 63 of the calling wavefront, which has to be a lane that calls it too: the value of a lane that has left the kernel, or that a partial
+// last wavefront never had, is not defined (the emulator returns what the slot held before, the hardware whatever the register holds).
 template <class T> KW_DEV T wave_scan_add(T v) {
     for (int d = 1; d < 64; d <<= 1) { T o = shfl_up(v, d); if (lane() >= d) v = v + o; }
     return v;

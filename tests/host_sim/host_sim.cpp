@@ -193,18 +193,30 @@ extern "C" int kai_hostsim_native_fill(double* ms, int64_t* launches, int64_t* d
     *ms = g_native_fill_ms; *launches = g_native_fill_launches; *decisions = g_native_fill_decisions; *diffs = g_native_fill_diffs;
     g_native_fill_ms = 0; g_native_fill_launches = g_native_fill_decisions = g_native_fill_diffs = 0; return 0;
 }
+// what the plan kernels were launched with since the last read (tests/test_batch_device_sizes.py asserts the sizes a run reached): the largest workgroup of kb_plan_scan and of
+// kb_plan_setup, the longest stream (positions) a kb_plan_scan workgroup and a segmented node took, the most segments a node was cut into, the segments' workgroup
+static int64_t g_plan_shapes[6] = {0, 0, 0, 0, 0, 0};
+static int64_t plan_longest_stream(const KaiCtx& c, int h) { int64_t m = 0; for (int i = c.bt.h_off[h]; i < c.bt.h_off[h + 1]; i++) m = std::max<int64_t>(m, c.bt.q_cnt[c.bt.h_nodes[i]]); return m; }
+extern "C" int kai_hostsim_plan_shapes(int64_t* out) { for (int i = 0; i < 6; i++) { out[i] = g_plan_shapes[i]; g_plan_shapes[i] = 0; } return 0; }
 // the batch path's kernels on the lock-step emulator (kai_simt.hpp)
 struct HostLauncher {
     void static_rank(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { kb_static_rank(c); }); }
     void static_check(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { kb_static_check(c); }); }
     void qualify(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { kb_qualify(c); }); }
     void nrec(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { kb_build_nrec(c); }); }
-    void plan_setup(int g, int b, const KaiCtx& c, RoundParams rp) { kw::launch(g, b, 0, [&] { kb_plan_setup(c, rp); }); }
+    void plan_setup(int g, int b, const KaiCtx& c, RoundParams rp) { g_plan_shapes[1] = std::max<int64_t>(g_plan_shapes[1], b); kw::launch(g, b, 0, [&] { kb_plan_setup(c, rp); }); }
     void plan_leaf(int g, int b, const KaiCtx& c, RoundParams rp) { kw::launch(g, b, 0, [&] { kb_plan_leaf(c, rp); }); }
     void plan_rank(int g, int b, const KaiCtx& c, RoundParams rp) { kw::launch(g, b, 0, [&] { kb_plan_rank(c, rp); }); }
     void plan_gather(int g, int b, const KaiCtx& c, RoundParams rp) { kw::launch(g, b, 0, [&] { kb_plan_gather(c, rp); }); }
-    void plan_scan(int g, int b, const KaiCtx& c, RoundParams rp) { kw::launch(g, b, 0, [&] { kb_plan_scan(c, rp); }); }
-    void seg_sum(int g, int b, const KaiCtx& c, RoundParams rp, int segs) { kw::launch(g, b, 0, [&] { kb_seg_sum(c, rp, segs); }); }
+    void plan_scan(int g, int b, const KaiCtx& c, RoundParams rp) {
+        kw::launch(g, b, 0, [&] { kb_plan_scan(c, rp); });
+        g_plan_shapes[0] = std::max<int64_t>(g_plan_shapes[0], b); g_plan_shapes[2] = std::max(g_plan_shapes[2], plan_longest_stream(c, rp.height));  // (q_cnt: as k_plan_setup of this round left it)
+    }
+    void seg_sum(int g, int b, const KaiCtx& c, RoundParams rp, int segs) {
+        kw::launch(g, b, 0, [&] { kb_seg_sum(c, rp, segs); });
+        const int64_t len = plan_longest_stream(c, rp.height);
+        g_plan_shapes[3] = std::max(g_plan_shapes[3], len); g_plan_shapes[4] = std::max<int64_t>(g_plan_shapes[4], (len + 1 + KPS_SEG - 1) / KPS_SEG); g_plan_shapes[5] = std::max<int64_t>(g_plan_shapes[5], b);
+    }
     void seg_gate(int g, int b, const KaiCtx& c, RoundParams rp, int segs) { kw::launch(g, b, 0, [&] { kb_seg_gate(c, rp, segs); }); }
     void seg_keys(int g, int b, const KaiCtx& c, RoundParams rp, int segs) { kw::launch(g, b, 0, [&] { kb_seg_keys(c, rp, segs); }); }
     void seg_max(int g, int b, const KaiCtx& c, RoundParams rp, int segs) { kw::launch(g, b, 0, [&] { kb_seg_max(c, rp, segs); }); }
