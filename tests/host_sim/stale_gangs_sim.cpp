@@ -1,61 +1,26 @@
 // stale_gangs_sim.cpp — TEST INFRASTRUCTURE: kai_stale_gang_eviction's kernel bodies and control flow (kai-scheduler_amd/csrc/kai_stale_gangs.hpp: sg_drive, and through it the
-// library's own oa_drive) compiled with plain g++ and run with the emulated lanes of kai_simt.hpp on a session set up exactly as the host simulation sets one up: this file
-// INCLUDES host_sim.cpp, as ops_apply_sim.cpp does.  tests/test_stale_gangs.py compares the decision with a numpy restatement of the reference's rules and the state with a TWIN
-// session that takes the same operations through kai_ops_apply's emulated apply (mode 1 below).  NOT a CPU fallback: libkai_core never contains it; the parity claim is
-// tests/test_gpu_stale_gangs.py on the MI355X.
+// library's own oa_drive) compiled with plain g++ and run with the emulated lanes of kai_simt.hpp on a session of the host simulation (sim_session.hpp: struct SimSession, opened
+// and driven as kai_hostsim_run drives one).  tests/test_stale_gangs.py compares the decision with a numpy restatement of the reference's rules and the state with a TWIN session
+// that takes the same operations through kai_ops_apply's emulated apply (mode 1 below: sim_session.hpp sim_ops_apply).  NOT a CPU fallback: libkai_core never contains it; the
+// parity claim is tests/test_gpu_stale_gangs.py on the MI355X.
 //
-// The call gets into kai_hostsim_run's cycle the way ops_apply_sim.cpp's batch does: job_init_state(c, 0) is the first thing every action calls; the name is routed through
-// sgsim_job_init_state for the text of host_sim.cpp only, and in front of action number `at` the hook runs the call.
+// The harness: open the session; run the actions `pre`; make the call on its context; copy the state right behind the call; run the actions `post`; read back.
 //
 // -DKAI_SGSIM_MAIN adds a main() with one fixed case (the stand-alone program the sanitizers are run on).
-#define KAI_SHARED_GPUS 1
-#include <cstdlib>
-#include <chrono>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <thread>
-#include <vector>
-namespace kai { extern int sgsim_dom_lanes_min; }
-#define KAI_DOM_LANES_MIN ::kai::sgsim_dom_lanes_min
-#include "../../kai-scheduler_amd/csrc/kai_host_prep.hpp"
-#include "../../kai-scheduler_amd/csrc/kai_batch_kernels.hpp"
-#include "../../kai-scheduler_amd/csrc/kai_batch_driver.hpp"
-#include "../../kai-scheduler_amd/csrc/kai_victim_shard.hpp"
+#include "sim_session.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_stale_gangs.hpp"
-#undef KAI_DOM_LANES_MIN
-namespace kai { int sgsim_dom_lanes_min = 16; }
-
-static uint8_t sgsim_job_init_state(const kai::KaiCtx& c, int j);
-#define job_init_state(c, j) sgsim_job_init_state(c, j)
-#include "host_sim.cpp"
-#undef job_init_state
 
 namespace {
 
-struct SgSim {
-    bool on = false; int at = 0, seen = 0, lanes = 256, mode = 0;
-    int64_t* since = nullptr; uint8_t* stale = nullptr; int64_t grace_ns = 0; uint32_t flags = 0; int64_t call_cap = 0;  // mode 0: the call's arguments
-    kai_op* ops = nullptr; int64_t n = 0; const uint32_t* rank = nullptr;  // mode 0: the evictions out (caller's node indices); mode 1: the batch in.  node index -> name rank
-    int status = 0; kai_stale_result res{}; int64_t n_ops_before = 0;
-    std::vector<int32_t> p_status, p_node, hidden; std::vector<double> n_idle, n_rel, n_used; std::vector<QShare> shares;  // the state right behind the call
-} g_sg;
-
 // the handle's scratch of both entry points: zero between calls
-struct Scratch { std::vector<int32_t> stamp, sh_status, sh_node, succ, first, wg_e, wg_f; std::vector<int64_t> since; std::vector<uint8_t> expired; std::vector<kai_op> ops; OaHead oa_head{}; SgHead head{}; };
-Scratch& scratch(const KaiCtx& c) {
-    static Scratch s;
-    if ((int)s.stamp.size() < c.P) { s.stamp.assign((size_t)c.P, 0); s.sh_status.assign((size_t)c.P, 0); s.sh_node.assign((size_t)c.P, 0); }
-    if ((int)s.succ.size() < c.J) s.succ.assign((size_t)c.J, 0);
-    return s;
-}
-
-struct SimLauncher {
+struct Scratch : ApplyScratch {
+    std::vector<int32_t> succ, first, wg_e, wg_f; std::vector<int64_t> since; std::vector<uint8_t> expired; std::vector<kai_op> ops; OaHead oa_head{}; SgHead head{};
+    void fit(const KaiCtx& c) { ApplyScratch::fit(c.P); if ((int)succ.size() < c.J) succ.assign((size_t)c.J, 0); }
+    bool clean(const KaiCtx& c) const { if (!ApplyScratch::clean(c.P)) return false; for (int j = 0; j < c.J; j++) if (succ[j]) return false; return true; }
+};
+struct SgLauncher : ApplyLauncher {
     Scratch& s;
-    void check(int g, int b, const KaiCtx& c, const OaArgs& a) { kw::launch(g, b, 0, [&] { oa_check_body(c, a); }); }
-    void wide(int g, int b, const KaiCtx& c, const OaArgs& a) { kw::launch(g, b, 0, [&] { oa_wide_body(c, a); }); }
-    int engine(const KaiCtx& c, const OaArgs& a) { KaiCtx cv = c; cv.use_index = 0; HostBackend be; oa_engine_walk(cv, be, a); return 0; }  // as k_oa_engine: one lane, no class index
-    int read_head(OaHead& hv, const OaArgs& a) { hv = *a.head; return 0; }
+    explicit SgLauncher(Scratch& sc) : s(sc) {}
     void succeeded(int g, int b, const KaiCtx& c, const SgArgs& a) { kw::launch(g, b, 0, [&] { sg_succeeded_body(c, a); }); }
     void jobs(int g, int b, const KaiCtx& c, const SgArgs& a) { kw::launch(g, b, 0, [&] { sg_jobs_body(c, a); }); }
     void first(int g, int b, const KaiCtx& c, const SgArgs& a) { kw::launch(g, b, 0, [&] { sg_first_body(c, a); }); }
@@ -66,82 +31,36 @@ struct SimLauncher {
     int reserve_ops(int n, SgArgs& a, OaArgs& oa) {
         s.ops.assign((size_t)n, kai_op{}); std::memset(&s.oa_head, 0xff, sizeof s.oa_head);  // (k_sg_emit writes the verdict's start values itself)
         a.oa_head = &s.oa_head; a.ops = s.ops.data();
-        oa.ops = s.ops.data(); oa.head = &s.oa_head; oa.stamp = s.stamp.data(); oa.sh_status = s.sh_status.data(); oa.sh_node = s.sh_node.data();
+        oa.ops = s.ops.data(); oa.head = &s.oa_head; s.bind(oa);
         return 0;
     }
 };
 
-bool scratch_clean(const KaiCtx& c, const Scratch& s) {
-    for (int p = 0; p < c.P; p++) if (s.stamp[p] || s.sh_status[p]) return false;
-    for (int j = 0; j < c.J; j++) if (s.succ[j]) return false;
-    return true;
-}
-void after_apply(KaiCtx& c) {  // the host side behind the kernels (kai_core.hip): index_stale, fast_ok
-    if (c.use_index) for (int b = 0; b < c.NB; b++) for (int k = 0; k < c.C; k++) HostBackend::build_block(c, k, b);
-    c.fast_ok = 0;
-}
-
-// kai_stale_gang_eviction from its first device call on (the refusals in front of it are host code of kai_core.hip, tested under tests/host_sim/fake_hip.cpp)
-void sgsim_call(KaiCtx& c) {
-    SgSim& g = g_sg; Scratch& s = scratch(c);
-    const int lanes = g.lanes, n_wgs = (int)(((int64_t)c.P + lanes - 1) / lanes);
-    s.since.assign(g.since, g.since + c.J); s.expired.assign((size_t)c.J, 0xee); s.first.assign((size_t)c.J, -7); s.wg_e.assign((size_t)n_wgs + 1, -7); s.wg_f.assign((size_t)n_wgs + 1, -7);
+// kai_stale_gang_eviction from its first device call on (the refusals in front of it are host code of kai_core.hip, tested under tests/host_sim/fake_hip.cpp):
+// since [J] in/out, stale_out [J] or NULL, ops_out [cap] (caller's node indices), *n_out; -> what the entry point would return
+int sim_stale_gangs(SimSession& ss, Scratch& s, int64_t* since, uint8_t* stale_out, int64_t grace_ns, uint32_t flags, int lanes, int64_t cap, kai_op* ops_out, int64_t* n_out, kai_stale_result& res) {
+    KaiCtx& c = ss.ctx(); s.fit(c);
+    const int n_wgs = (int)(((int64_t)c.P + lanes - 1) / lanes);
+    s.since.assign(since, since + c.J); s.expired.assign((size_t)c.J, 0xee); s.first.assign((size_t)c.J, -7); s.wg_e.assign((size_t)n_wgs + 1, -7); s.wg_f.assign((size_t)n_wgs + 1, -7);
     s.head = SgHead{};
-    SgArgs a{}; a.now_ns = c.now_ns; a.grace_ns = g.grace_ns; a.n_wgs = n_wgs;
+    SgArgs a{}; a.now_ns = c.now_ns; a.grace_ns = grace_ns; a.n_wgs = n_wgs;
     a.head = &s.head; a.since = s.since.data(); a.expired = s.expired.data(); a.succ = s.succ.data(); a.first = s.first.data(); a.wg_e = s.wg_e.data(); a.wg_f = s.wg_f.data();
-    SimLauncher l{s}; SgHead hd{}; OaHead hv{}; int path = 0;
-    const bool dry = (g.flags & KAI_STALE_DRY_RUN) != 0;
-    g.status = sg_drive(l, c, a, lanes, dry, g.call_cap, hd, hv, path);
-    if (!scratch_clean(c, s)) g.status = KAI_ERR_DEVICE_FAULT;
-    if (g.status == KAI_ERR_CAPACITY) { g.n = hd.n_ops; return; }
-    if (g.status != KAI_OK) return;
-    if (hd.n_ops > 0 && !dry) after_apply(c);
-    std::vector<int32_t> caller_of((size_t)std::max(c.N, 1)); for (int n = 0; n < c.N; n++) caller_of[g.rank[n]] = n;
-    std::memcpy(g.since, s.since.data(), (size_t)c.J * 8);
-    if (g.stale) std::memcpy(g.stale, s.expired.data(), (size_t)c.J);
-    for (int i = 0; i < hd.n_ops; i++) { kai_op o = s.ops[(size_t)i]; o.node = caller_of[o.node]; g.ops[i] = o; }
-    g.n = hd.n_ops;
-    g.res.stale_jobs = hd.stale_jobs; g.res.expired_jobs = hd.expired_jobs; g.res.n_ops = hd.n_ops; g.res.path = path; g.res.pad = 0;
-}
-
-// mode 1, the twin: kai_ops_apply from its first device call on, as ops_apply_sim.cpp's oasim_call
-void oasim_call(KaiCtx& c) {
-    SgSim& g = g_sg; Scratch& s = scratch(c);
-    const int n = (int)g.n;
-    if (!n) return;
-    std::vector<kai_op> ops(g.ops, g.ops + n);
-    for (int i = 0; i < n; i++) ops[i].node = (int32_t)g.rank[ops[i].node];
-    OaHead head{}; head.bad = KAI_OA_NONE;
-    OaArgs a{}; a.n = n; a.flags = oa_wide_session(c) ? 0u : KAI_OA_NOT_WIDE; a.use_islot = oa_use_islot(c);
-    a.ops = ops.data(); a.head = &head; a.stamp = s.stamp.data(); a.sh_status = s.sh_status.data(); a.sh_node = s.sh_node.data();
-    SimLauncher l{s}; OaHead hv{}; int path = 0;
-    g.status = oa_drive(l, c, a, g.lanes, hv, path);
-    if (!scratch_clean(c, s)) g.status = KAI_ERR_DEVICE_FAULT;
-    if (g.status == KAI_OK) { g.res.path = path; g.res.n_ops = n; after_apply(c); }
-}
-
-void sgsim_apply(KaiCtx& c) {
-    SgSim& g = g_sg;
-    g.n_ops_before = c.st->out_len;
-    if (g.at == 0) for (int q = 0; q < c.Q; q++) qnode_init(c, q, 0);  // k_qnode_static of the open: the host simulation fills the tree in its first action only, and the event handlers walk its parents
-    if (g.mode == 0) sgsim_call(c); else oasim_call(c);
-    g.p_status.assign(c.p_status, c.p_status + c.P); g.p_node.assign(c.p_node, c.p_node + c.P);
-    g.n_idle.assign(c.n_idle, c.n_idle + (size_t)c.R * c.N); g.n_rel.assign(c.n_rel, c.n_rel + (size_t)c.R * c.N); g.n_used.assign(c.n_used, c.n_used + (size_t)c.R * c.N);
-    g.shares.assign(c.q_share, c.q_share + (size_t)c.Q * 3);
-    // what no read-back shows, as one comparable record per pod / pod-set / job
-    g.hidden.clear();
-    for (int p = 0; p < c.P; p++) { g.hidden.push_back(c.p_on_node[p]); g.hidden.push_back(c.p_on_node[p] >= 0 ? c.p_on_node_status[p] : 0); g.hidden.push_back(c.p_accepted[p]); g.hidden.push_back(c.p_virtual[p]); }
-    for (int s = 0; s < c.S; s++) { g.hidden.push_back(c.s_active_alloc[s]); g.hidden.push_back(c.s_active_used[s]); g.hidden.push_back(c.s_alive[s]); g.hidden.push_back(c.s_pipelined[s]); }
-    for (int j = 0; j < c.J; j++) { g.hidden.push_back(c.j_n_pending[j]); g.hidden.push_back(c.j_tta_valid[j]); for (int k = 0; k < 3; k++) { int64_t b; std::memcpy(&b, &c.j_allocated[(size_t)j * 4 + k], 8); g.hidden.push_back((int32_t)b); g.hidden.push_back((int32_t)(b >> 32)); } }
-    g.hidden.push_back(c.fast_ok);
+    SgLauncher l{s}; SgHead hd{}; OaHead hv{}; int path = 0;
+    const bool dry = (flags & KAI_STALE_DRY_RUN) != 0;
+    int status = sg_drive(l, c, a, lanes, dry, cap, hd, hv, path);
+    if (!s.clean(c)) status = KAI_ERR_DEVICE_FAULT;
+    if (status == KAI_ERR_CAPACITY) *n_out = hd.n_ops;  // the count needed; nothing else is written
+    if (status != KAI_OK) return status;
+    if (hd.n_ops > 0 && !dry) ss.state_written(true);  // as kai_ops_apply leaves the handle after evictions
+    std::memcpy(since, s.since.data(), (size_t)c.J * 8);
+    if (stale_out) std::memcpy(stale_out, s.expired.data(), (size_t)c.J);
+    for (int i = 0; i < hd.n_ops; i++) { kai_op o = s.ops[(size_t)i]; o.node = ss.caller_node(o.node); ops_out[i] = o; }
+    *n_out = hd.n_ops;
+    res.stale_jobs = hd.stale_jobs; res.expired_jobs = hd.expired_jobs; res.n_ops = hd.n_ops; res.path = path; res.pad = 0;
+    return status;
 }
 
 }  // namespace
-
-static uint8_t sgsim_job_init_state(const kai::KaiCtx& c, int j) {
-    if (j == 0 && g_sg.on && g_sg.seen++ == g_sg.at) sgsim_apply(const_cast<kai::KaiCtx&>(c));  // (the context is kai_hostsim_run's own, non-const object)
-    return job_init_state(c, j);
-}
 
 extern "C" {
 
@@ -149,54 +68,33 @@ extern "C" {
 //   mode 0: kai_stale_gang_eviction at the clock cfg->now_ns with `grace_ns`, `flags` (KAI_STALE_DRY_RUN) and a capacity of `call_cap` operations, in workgroups of `lanes` lanes:
 //           since [J] in/out, stale_out [J] or NULL, sg_ops [call_cap] out, *n_sg_ops out, result out;
 //   mode 1: kai_ops_apply's emulated apply of sg_ops[0 .. *n_sg_ops) (the twin);
-// then the actions `post`.  call_status: what the entry point would return.  mid_* / hidden: the state right behind the call (hidden: what no read-back shows, as int32 words:
-// per pod p_on_node, its status, p_accepted, p_virtual; per pod-set active_alloc, active_used, alive, pipelined; per job n_pending, j_tta_valid, j_allocated's bits; fast_ok).
-// ops_out ...: the operations of ALL actions and the final state, as kai_hostsim_run returns them.  With no post action the cycle is given one allocate to carry the hook; its
-// results are dropped (the final state then is the state behind the call).
+// then the actions `post`.  call_status: what the entry point would return.  mid_* / hidden: the state right behind the call (hidden: sim_session.hpp StateCopy's words, then fast_ok).
+// ops_out ...: the operations of ALL actions and the final state, as kai_hostsim_run returns them (no post action: the state behind the call).
 int kai_sgsim_run(const kai_config* cfg, const kai_snapshot_soa* s, const int* pre, int n_pre, int mode, int64_t* since, uint8_t* stale_out, int64_t grace_ns, uint32_t flags, int lanes,
                   int64_t call_cap, kai_op* sg_ops, int64_t* n_sg_ops, kai_stale_result* result, int* call_status, const int* post, int n_post,
                   int32_t* mid_status, int32_t* mid_node, kai_queue_share* mid_shares, kai_node_state* mid_nodes, int32_t* hidden, int64_t hidden_cap, int64_t* n_hidden,
                   kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, int32_t* pod_status_out, int32_t* pod_node_out, kai_queue_share* shares_final, kai_node_state* nodes_out) {
     if (!cfg || !s || n_pre < 0 || n_post < 0 || lanes < 1 || lanes > 4096 || s->n_jobs < 1 || !n_sg_ops || (mode != 0 && mode != 1) || (mode == 0 && (!since || call_cap < 0))) return KAI_ERR_INVALID_ARG;
-    { std::vector<char> seen_rank((size_t)std::max(s->n_nodes, 1), 0); for (int n = 0; n < s->n_nodes; n++) { const uint32_t rk = s->node_name_rank[n]; if (rk >= (uint32_t)s->n_nodes || seen_rank[rk]) return KAI_ERR_INVALID_ARG; seen_rank[rk] = 1; } }
     if (mode == 1) for (int64_t i = 0; i < *n_sg_ops; i++) if (sg_ops[i].node < 0 || sg_ops[i].node >= s->n_nodes || sg_ops[i].pod < 0 || sg_ops[i].pod >= s->n_pods || sg_ops[i].kind < 0 || sg_ops[i].kind > 2) return KAI_ERR_INVALID_ARG;
-    std::vector<int> acts(pre, pre + n_pre); acts.insert(acts.end(), post, post + n_post);
-    const bool carrier = n_post == 0;
-    if (carrier) acts.push_back(KAI_ACTION_ALLOCATE);
-    g_sg = SgSim{}; g_sg.on = true; g_sg.at = n_pre; g_sg.lanes = lanes; g_sg.mode = mode; g_sg.since = since; g_sg.stale = stale_out; g_sg.grace_ns = grace_ns; g_sg.flags = flags; g_sg.call_cap = call_cap;
-    g_sg.ops = sg_ops; g_sg.n = mode == 1 ? *n_sg_ops : 0; g_sg.rank = s->node_name_rank;
-    std::vector<kai_op> all((size_t)ops_cap + 1); int64_t n_all = 0;
-    const bool had_nb = std::getenv("KAI_HOSTSIM_NO_BATCH") != nullptr;
-    if (carrier && !had_nb) setenv("KAI_HOSTSIM_NO_BATCH", "1", 1);  // the carrier's results are dropped: the sequential engine gets through it far sooner than the emulated batch path
-    const int rc = kai_hostsim_run(cfg, s, acts.data(), (int)acts.size(), all.data(), ops_cap, &n_all, pod_status_out, pod_node_out, nullptr, shares_final, nodes_out, nullptr, nullptr);
-    if (carrier && !had_nb) unsetenv("KAI_HOSTSIM_NO_BATCH");
-    const SgSim g = g_sg; g_sg = SgSim{};
-    if (rc) return rc;
-    if (g.seen <= g.at) { std::fprintf(stderr, "stale_gangs_sim: kai_hostsim_run did not pass job_init_state(c, 0) in front of action %d: the call was never made (host_sim.cpp changed?)\n", g.at); return KAI_ERR_STATE; }
-    const int N = s->n_nodes, P = s->n_pods, Q = s->n_queues, R = s->n_res;
-    if (call_status) *call_status = g.status;
-    if (result) *result = g.res;
-    if (mode == 0) *n_sg_ops = g.n;
-    auto put_shares = [&](kai_queue_share* out) { for (int q = 0; q < Q; q++) for (int k = 0; k < 3; k++) { const QShare& x = g.shares[(size_t)q * 3 + k];
-        out[q].fair_share[k] = x.fair; out[q].allocated[k] = x.allocated; out[q].allocated_non_preemptible[k] = x.allocated_np; out[q].request[k] = x.request; out[q].deserved[k] = x.deserved; out[q].max_allowed[k] = x.max_allowed; } };
-    auto put_nodes = [&](kai_node_state* out) { for (int n = 0; n < N; n++) { kai_node_state o; std::memset(&o, 0, sizeof o); const int e = (int)s->node_name_rank[n];
-        for (int r = 0; r < R; r++) { o.idle[r] = g.n_idle[(size_t)r * N + e]; o.releasing[r] = g.n_rel[(size_t)r * N + e]; o.used[r] = g.n_used[(size_t)r * N + e]; } out[n] = o; } };
-    std::vector<int32_t> caller_of((size_t)std::max(N, 1)); for (int n = 0; n < N; n++) caller_of[s->node_name_rank[n]] = n;
-    if (mid_status) std::memcpy(mid_status, g.p_status.data(), (size_t)P * 4);
-    if (mid_node) for (int p = 0; p < P; p++) mid_node[p] = g.p_node[p] >= 0 ? caller_of[g.p_node[p]] : -1;
-    if (mid_shares) put_shares(mid_shares);
-    if (mid_nodes) put_nodes(mid_nodes);
-    if (n_hidden) *n_hidden = (int64_t)g.hidden.size();
-    if (hidden) { if ((int64_t)g.hidden.size() > hidden_cap) return KAI_ERR_CAPACITY; std::memcpy(hidden, g.hidden.data(), g.hidden.size() * 4); }
-    if (carrier) {  // drop the carrier action: the final state is the one behind the call, its operations are not the caller's
-        if (pod_status_out) std::memcpy(pod_status_out, g.p_status.data(), (size_t)P * 4);
-        if (pod_node_out) for (int p = 0; p < P; p++) pod_node_out[p] = g.p_node[p] >= 0 ? caller_of[g.p_node[p]] : -1;
-        if (shares_final) put_shares(shares_final);
-        if (nodes_out) put_nodes(nodes_out);
-        n_all = g.n_ops_before;
+    SimSession ss;
+    if (int rc = ss.open(cfg, s, n_pre + n_post, n_post > 0)) return rc;  // (as it always was: without a post action, `pre` runs on the sequential engine, as in ops_apply_sim.cpp)
+    for (int i = 0; i < n_pre; i++) if (int rc = ss.action(pre[i])) return rc;
+    static Scratch scratch; scratch.fit(ss.ctx()); int status = KAI_OK; kai_stale_result res{};
+    if (mode == 0) { *n_sg_ops = 0; status = sim_stale_gangs(ss, scratch, since, stale_out, grace_ns, flags, lanes, call_cap, sg_ops, n_sg_ops, res); }
+    else if (*n_sg_ops > 0) {
+        kai_apply_result ar{};
+        status = sim_ops_apply(ss, scratch, sg_ops, (int)*n_sg_ops, 0, lanes, ar);
+        if (!scratch.clean(ss.ctx())) status = KAI_ERR_DEVICE_FAULT;
+        if (status == KAI_OK) { res.path = ar.path; res.n_ops = (int)*n_sg_ops; ss.state_written(true); }  // as kai_stale_gang_eviction leaves the handle after its evictions
     }
-    if (n_ops) *n_ops = n_all;
-    if (ops_out) std::memcpy(ops_out, all.data(), (size_t)n_all * sizeof(kai_op));
+    StateCopy mid = ss.snapshot_state(); mid.hidden.push_back(ss.ctx().fast_ok);
+    for (int i = 0; i < n_post; i++) if (int rc = ss.action(post[i])) return rc;
+    if (int rc = ss.finish()) return rc;
+    if (call_status) *call_status = status;
+    if (result) *result = res;
+    if (int rc = ss.write(mid, mid_status, mid_node, mid_shares, mid_nodes, hidden, hidden_cap, n_hidden)) return rc;
+    if (int rc = ss.ops(ops_out, ops_cap, n_ops)) return rc;
+    ss.pod_state(pod_status_out, pod_node_out); ss.shares(shares_final); ss.nodes(nodes_out);
     return KAI_OK;
 }
 

@@ -162,7 +162,7 @@ SIM_SRC = os.path.join(ROOT, "tests", "host_sim", "stale_gangs_sim.cpp")
 
 def sim_lib():
     so = os.path.join(ROOT, "tests", "host_sim", "libstalegangssim.so")
-    deps = [SIM_SRC, os.path.join(ROOT, "tests", "host_sim", "host_sim.cpp"), os.path.join(ROOT, "tests", "host_sim", "native_bucket_fill.hpp")] + \
+    deps = [SIM_SRC, os.path.join(ROOT, "tests", "host_sim", "sim_session.hpp"), os.path.join(ROOT, "tests", "host_sim", "native_bucket_fill.hpp")] + \
         glob.glob(os.path.join(ROOT, "kai-scheduler_amd", "csrc", "*.hpp")) + glob.glob(os.path.join(ROOT, "kai-scheduler_amd", "csrc", "*.inc")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", "-pthread", "-o", so, SIM_SRC])
