@@ -492,6 +492,28 @@ typedef struct kai_node_answer { int32_t node; int32_t is_pipeline; } kai_node_a
 int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries,
                    const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out);
 
+/* The first k entries of the list kai_best_nodes answers the head of, for MANY tasks in one chip-wide pass.  For queries[i] take the node set of
+ * kai_best_nodes (row queries[i].nodeset of nodeset_bitmaps, or all nodes for -1) and let L be Session.OrderedNodesByTask(nodeSet, task)
+ * (framework/session.go:201-264: best score first, name rank on ties) with the nodes that fail FittingNode dropped, at the session's current state.
+ * Then n_out[i] = min(k, |L|), out[i*k + j] for j < n_out[i] is the caller's index of L[j] with is_pipeline = PIPELINE_ONLY || !IsTaskAllocatable(task, L[j])
+ * — the per-node rule kai_best_node applies to its one answer — and the entries j >= n_out[i] are {-1, 0}.  A task over its queue's capacity has n_out[i] = 0.
+ * This is the list the reference's allocation walks (actions/common/allocate.go): a caller with a filter of its own (inter-pod affinity, host ports, volumes, DRA:
+ * KAI_POD_CPU_FALLBACK pods) runs it down the list and stops at the first pass.  With k = 1 the call is kai_best_nodes, answer for answer.
+ * The list is NOT "kai_best_node again with the winners removed from the node set": under a bin-pack strategy NodePreOrderFn
+ * (plugins/nodeplacement/pack.go:66-86) takes the minimum and maximum of Idle + Releasing over the node set it is given, so removing a node can move them and
+ * rescale every pack score against the other plugins' fixed scores.  Here the range is taken ONCE, over the whole node set, as the reference takes it.
+ * The call changes nothing: read-backs, kai_action_stats_get and every later action are as if it had not happened.  It does not look at the pod's status;
+ * duplicate queries are allowed.
+ * n_queries == 0: KAI_OK without a launch.  KAI_ERR_INVALID_ARG: everything kai_best_nodes refuses, k < 1 or k > KAI_ORDERED_MAX_K, a NULL out or n_out with
+ * n_queries > 0.  KAI_ERR_CAPACITY: n_queries * k above 2^27.  KAI_ERR_STATE: no open session.  KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1).
+ * Every refusal is decided before the first device call and leaves out and n_out untouched and the session open.
+ * On the device: one staging upload, three launches (k_bn_prep, k_bn_range, k_on_scan; kai_ordered_nodes.hpp), one download and one stream synchronise; every
+ * node is scored once per query, whatever k.  The scratch is kai_best_nodes': it belongs to the handle, grows on demand and is freed by kai_core_destroy. */
+#define KAI_ORDERED_MAX_K 64
+int kai_ordered_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries,
+                      const uint32_t* nodeset_bitmaps, int32_t n_nodesets, int32_t k,
+                      kai_node_answer* out /* [n_queries][k] */, int32_t* n_out /* [n_queries] */);
+
 /* Committed operations taken back INTO the open session: what framework.Statement does with them (framework/statement.go), for operations an action of this
  * handle did not commit itself — an action the Go scheduler ran after a fallback, the operations of another handle (a standby scheduler, a what-if session).
  * The operations are taken in array order.  Each maximal run of equal `stmt` is one Statement: KAI_OP_ALLOCATE is Statement.Allocate(pod, node),

@@ -216,6 +216,7 @@ class KaiOp(C.Structure):
 
 
 QUERY_PIPELINE_ONLY = 0x1  # KAI_QUERY_PIPELINE_ONLY
+ORDERED_MAX_K = 64         # KAI_ORDERED_MAX_K: the longest list kai_ordered_nodes returns per task
 
 
 class KaiNodeQuery(C.Structure):

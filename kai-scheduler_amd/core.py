@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ops_apply", "kai_stale_gang_eviction",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -124,6 +124,7 @@ def load_library(path: str = LIB_PATH):
     lib.kai_action_execute.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64)]
     lib.kai_best_node.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
     lib.kai_best_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiNodeAnswer)]
+    lib.kai_ordered_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(abi.KaiNodeAnswer), C.POINTER(C.c_int32)]
     lib.kai_ops_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiApplyResult)]
     lib.kai_stale_gang_eviction.argtypes = [C.c_void_p, C.POINTER(abi.KaiStaleParams), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(abi.KaiOp), C.c_int64,
                                             C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
@@ -300,10 +301,8 @@ class Session:
         self.core._check(self.core.lib.kai_best_node(self.core.handle, pod, bits, int(pipeline_only), C.byref(node), C.byref(pipe)))
         return node.value, bool(pipe.value)
 
-    def best_nodes(self, pods, nodesets=None, nodeset_of=None, pipeline_only=None):
-        """kai_best_nodes: best_node for many tasks in one chip-wide pass.  pods: pod indices; nodesets: node sets as index lists or boolean masks over the
-        nodes; nodeset_of: per pod its set in `nodesets` (-1 / None = all nodes); pipeline_only: one bool for all or one per pod.
-        Returns (node, is_pipeline): an int32 array (-1 = nothing fits) and a bool array."""
+    def _node_queries(self, pods, nodesets, nodeset_of, pipeline_only):
+        """The arguments best_nodes and ordered_nodes share, as kai_node_query records and node-set rows: (q, words, n_sets)."""
         pods = np.ascontiguousarray(pods, dtype=np.int32).ravel()
         M, N = len(pods), self.snap.n_nodes
         W = (N + 31) // 32
@@ -322,11 +321,32 @@ class Session:
         q["nodeset"] = -1 if nodeset_of is None else np.array([-1 if s is None else int(s) for s in np.asarray(nodeset_of, dtype=object).ravel()], dtype=np.int32)
         if pipeline_only is not None:
             q["flags"] = np.where(np.broadcast_to(np.asarray(pipeline_only, dtype=bool), (M,)), abi.QUERY_PIPELINE_ONLY, 0)
+        return q, words, len(sets)
+
+    def best_nodes(self, pods, nodesets=None, nodeset_of=None, pipeline_only=None):
+        """kai_best_nodes: best_node for many tasks in one chip-wide pass.  pods: pod indices; nodesets: node sets as index lists or boolean masks over the
+        nodes; nodeset_of: per pod its set in `nodesets` (-1 / None = all nodes); pipeline_only: one bool for all or one per pod.
+        Returns (node, is_pipeline): an int32 array (-1 = nothing fits) and a bool array."""
+        q, words, n_sets = self._node_queries(pods, nodesets, nodeset_of, pipeline_only)
+        M = len(q)
         out = np.zeros(M, dtype=np.dtype([("node", "<i4"), ("is_pipeline", "<i4")]))  # kai_node_answer
         self.core._check(self.core.lib.kai_best_nodes(self.core.handle, q.ctypes.data_as(C.POINTER(abi.KaiNodeQuery)), M,
-                                                      words.ctypes.data_as(C.POINTER(C.c_uint32)) if sets else None, len(sets),
+                                                      words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_sets else None, n_sets,
                                                       out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer))))
         return out["node"].copy(), out["is_pipeline"].astype(bool)
+
+    def ordered_nodes(self, pods, k, nodesets=None, nodeset_of=None, pipeline_only=None):
+        """kai_ordered_nodes: per task the first k (1 .. abi.ORDERED_MAX_K) nodes of Session.OrderedNodesByTask that pass FittingNode, best first — the list the
+        reference's allocation walks, of which best_nodes answers the head.  The arguments are best_nodes'.
+        Returns (node [M, k] int32, is_pipeline [M, k] bool, count [M] int32): row i holds count[i] nodes, then -1 / False."""
+        q, words, n_sets = self._node_queries(pods, nodesets, nodeset_of, pipeline_only)
+        M, k = len(q), int(k)
+        out = np.zeros((M, max(k, 1)), dtype=np.dtype([("node", "<i4"), ("is_pipeline", "<i4")]))  # kai_node_answer
+        count = np.zeros(max(M, 1), np.int32)
+        self.core._check(self.core.lib.kai_ordered_nodes(self.core.handle, q.ctypes.data_as(C.POINTER(abi.KaiNodeQuery)), M,
+                                                         words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_sets else None, n_sets, k,
+                                                         out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer)), count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out["node"].copy(), out["is_pipeline"].astype(bool), count[:M]
 
     def apply_ops(self, ops, check_only: bool = False, engine_path: bool = False):
         """kai_ops_apply: committed operations taken back into the session, as framework.Statement applies and commits them — `ops` is the array `execute` returns

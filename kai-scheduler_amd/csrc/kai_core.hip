@@ -151,31 +151,36 @@ int kai_best_node(kai_core* core, int32_t pod_idx, const uint32_t* nodeset_bitma
     return KAI_OK;
 }
 
-int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out) {
-    // every refusal before the first device call; `out` is written only after the answers came back
-    if (!core) return KAI_ERR_INVALID_ARG;
-    if (n_queries < 0 || n_nodesets < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: a negative count");
-    if (n_queries > 0 && (!queries || !out)) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: queries / out is NULL");
-    if (n_nodesets > 0 && !nodeset_bitmaps) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: nodeset_bitmaps is NULL");
-    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_best_nodes: a handle of a sharded group");
+// What kai_best_nodes and kai_ordered_nodes refuse alike, in one pass and before the first device call.  *empty: an accepted call without queries (KAI_OK, nothing to do)
+static int bn_check(kai_core* core, const char* who, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, bool out_null, bool* empty) {
+    auto no = [&](int code, const char* why) { core->err = std::string(who) + ": " + why; return code; };
+    *empty = false;
+    if (n_queries < 0 || n_nodesets < 0) return no(KAI_ERR_INVALID_ARG, "a negative count");
+    if (n_queries > 0 && (!queries || out_null)) return no(KAI_ERR_INVALID_ARG, "queries / out is NULL");
+    if (n_nodesets > 0 && !nodeset_bitmaps) return no(KAI_ERR_INVALID_ARG, "nodeset_bitmaps is NULL");
+    if (core->world > 1) return no(KAI_ERR_UNSUPPORTED, "a handle of a sharded group");
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
-    if (n_queries == 0) return KAI_OK;
-    const int N = core->ctx.N, P = core->ctx.P, M = n_queries, S = n_nodesets, W = (N + 31) / 32;
-    for (int i = 0; i < M; i++) {
+    if (n_queries == 0) { *empty = true; return KAI_OK; }
+    const int P = core->ctx.P, S = n_nodesets;
+    for (int i = 0; i < n_queries; i++) {
         const kai_node_query& q = queries[i];
-        if (q.pod < 0 || q.pod >= P) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: pod index out of range");
-        if (q.nodeset < -1 || q.nodeset >= S) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: nodeset outside -1 .. n_nodesets-1");
-        if (q.flags & ~KAI_QUERY_PIPELINE_ONLY) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: unknown flag bits");
-        if (q.pad != 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_best_nodes: pad is not zero");
+        if (q.pod < 0 || q.pod >= P) return no(KAI_ERR_INVALID_ARG, "pod index out of range");
+        if (q.nodeset < -1 || q.nodeset >= S) return no(KAI_ERR_INVALID_ARG, "nodeset outside -1 .. n_nodesets-1");
+        if (q.flags & ~KAI_QUERY_PIPELINE_ONLY) return no(KAI_ERR_INVALID_ARG, "unknown flag bits");
+        if (q.pad != 0) return no(KAI_ERR_INVALID_ARG, "pad is not zero");
     }
-    HIP_TRY(core, hipSetDevice(core->device));
-    const BnLayout L(N, M, S, W);
-    bool grew = false;  // scratch and staging growth: the only allocations, none once the handle is warm
-    KAI_TRY(reserve(core, core->bn_dev, L.end, std::max<size_t>(L.end + L.end / 2, (size_t)1 << 16), &grew));
+    return KAI_OK;
+}
+
+// The part of a call the two share: the handle's scratch (dev_bytes) and staging ([what is sent][down_bytes of answers]) grown on demand — the only allocations, none once the
+// handle is warm —, ONE staging upload and the launches of k_bn_prep and k_bn_range.  The permutation lies at offset 0 of the scratch whichever of the two calls sized it.
+static int bn_stage(kai_core* core, const BnLayout& L, size_t dev_bytes, size_t down_bytes, const kai_node_query* queries, const uint32_t* nodeset_bitmaps, int M, int S, int W, BnArgs& a) {
+    const int N = core->ctx.N;
+    bool grew = false;
+    KAI_TRY(reserve(core, core->bn_dev, dev_bytes, std::max<size_t>(dev_bytes + dev_bytes / 2, (size_t)1 << 16), &grew));
     if (grew) core->bn_perm_ok = false;  // (the new scratch does not hold the permutation)
-    const size_t pin_need = L.up_end + (size_t)M * sizeof(kai_node_answer) + 16;  // [what is sent][the answers]
+    const size_t pin_need = L.up_end + down_bytes + 16;
     KAI_TRY(reserve(core, core->bn_pin, pin_need, std::max<size_t>(pin_need + pin_need / 2, (size_t)1 << 16)));
-    const int cus = device_cus(core);
     // ---- one staging upload: [queries | rows | zeroed need flags], behind the permutation when the scratch does not hold this session's yet
     unsigned char* h = core->bn_pin.p; unsigned char* d = core->bn_dev.p;
     const size_t up0 = core->bn_perm_ok ? L.queries : L.perm;
@@ -185,12 +190,11 @@ int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_quer
     std::memset(h + L.need, 0, L.up_end - L.need);
     HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, L.up_end - up0, hipMemcpyHostToDevice, core->stream));
     core->bn_perm_ok = true;
-    BnArgs a{};
+    a = BnArgs{};
     a.M = M; a.S = S; a.W = W;
     a.queries = (KAI_GP(const kai_node_query))(d + L.queries); a.rows_in = (KAI_GP(const uint32_t))(d + L.rows_in); a.perm = (KAI_GP(const int32_t))(d + L.perm);
     a.rows = (KAI_GP(uint32_t))(d + L.rows); a.need = (KAI_GP(int32_t))(d + L.need); a.range = (KAI_GP(double))(d + L.range);
     a.prep = (KAI_GP(BnQuery))(d + L.prep); a.out = (KAI_GP(kai_node_answer))(d + L.out);
-    // ---- three launches
     const size_t prep_items = std::max<size_t>((size_t)M, (size_t)S * W);
     hipLaunchKernelGGL(k_bn_prep, dim3((unsigned)((prep_items + KAI_BN_WG - 1) / KAI_BN_WG)), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
     HIP_TRY(core, hipGetLastError());
@@ -199,14 +203,58 @@ int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_quer
         hipLaunchKernelGGL(k_bn_range, dim3((unsigned)(2 * (S + 1))), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
         HIP_TRY(core, hipGetLastError());
     }
+    return KAI_OK;
+}
+
+int kai_best_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, kai_node_answer* out) {
+    // every refusal before the first device call; `out` is written only after the answers came back
+    if (!core) return KAI_ERR_INVALID_ARG;
+    bool empty = false;
+    KAI_TRY(bn_check(core, "kai_best_nodes", queries, n_queries, nodeset_bitmaps, n_nodesets, !out, &empty));
+    if (empty) return KAI_OK;
+    const int N = core->ctx.N, M = n_queries, S = n_nodesets, W = (N + 31) / 32;
+    HIP_TRY(core, hipSetDevice(core->device));
+    const BnLayout L(N, M, S, W);
+    const int cus = device_cus(core);
+    BnArgs a;
+    KAI_TRY(bn_stage(core, L, L.end, (size_t)M * sizeof(kai_node_answer), queries, nodeset_bitmaps, M, S, W, a));  // the upload and two of the three launches
     const int grid = std::min(M, cus * KAI_BN_WGS_PER_CU);
     hipLaunchKernelGGL(k_bn_scan, dim3((unsigned)grid), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a);
     HIP_TRY(core, hipGetLastError());
     // ---- one download, one synchronise
-    unsigned char* h_out = h + L.up_end;
-    HIP_TRY(core, hipMemcpyAsync(h_out, d + L.out, (size_t)M * sizeof(kai_node_answer), hipMemcpyDeviceToHost, core->stream));
+    unsigned char* h_out = core->bn_pin.p + L.up_end;
+    HIP_TRY(core, hipMemcpyAsync(h_out, core->bn_dev.p + L.out, (size_t)M * sizeof(kai_node_answer), hipMemcpyDeviceToHost, core->stream));
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     std::memcpy(out, h_out, (size_t)M * sizeof(kai_node_answer));
+    return KAI_OK;
+}
+
+int kai_ordered_nodes(kai_core* core, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, int32_t k,
+                      kai_node_answer* out, int32_t* n_out) {
+    // every refusal before the first device call; `out` and `n_out` are written only after the lists came back
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (k < 1 || k > KAI_ORDERED_MAX_K) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes: k outside 1 .. KAI_ORDERED_MAX_K");
+    bool empty = false;
+    KAI_TRY(bn_check(core, "kai_ordered_nodes", queries, n_queries, nodeset_bitmaps, n_nodesets, !out || !n_out, &empty));
+    if (empty) return KAI_OK;
+    if ((int64_t)n_queries * k > ((int64_t)1 << 27)) return fail(core, KAI_ERR_CAPACITY, "kai_ordered_nodes: n_queries * k above 2^27");
+    const int N = core->ctx.N, M = n_queries, S = n_nodesets, W = (N + 31) / 32;
+    HIP_TRY(core, hipSetDevice(core->device));
+    const OnLayout L(N, M, S, W, k);
+    const int cus = device_cus(core);
+    BnArgs a;
+    KAI_TRY(bn_stage(core, L, L.on_end, L.down_bytes(M, k), queries, nodeset_bitmaps, M, S, W, a));  // the upload and two of the three launches
+    OnArgs o{};
+    o.k = k; o.out = (KAI_GP(kai_node_answer))(core->bn_dev.p + L.lists); o.n_out = (KAI_GP(int32_t))(core->bn_dev.p + L.n_out);
+    const int grid = std::min(M, cus * KAI_BN_WGS_PER_CU);
+    hipLaunchKernelGGL(k_on_scan, dim3((unsigned)grid), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a, o);
+    HIP_TRY(core, hipGetLastError());
+    // ---- one download ([the lists | their lengths]), one synchronise
+    unsigned char* h_out = core->bn_pin.p + L.up_end;
+    HIP_TRY(core, hipMemcpyAsync(h_out, core->bn_dev.p + L.lists, L.down_bytes(M, k), hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    std::memcpy(out, h_out, (size_t)M * k * sizeof(kai_node_answer));
+    std::memcpy(n_out, h_out + (L.n_out - L.lists), (size_t)M * 4);
     return KAI_OK;
 }
 

@@ -22,6 +22,7 @@
 #include "kai_victim_shard.hpp"
 #include "kai_delta.hpp"
 #include "kai_best_nodes.hpp"
+#include "kai_ordered_nodes.hpp"
 #include "kai_ops_apply.hpp"
 #include "kai_stale_gangs.hpp"
 
@@ -104,7 +105,7 @@ struct kai_core {
     int cls_cap = 0;  // classes the session's cls / sum1_key / sum1_node arrays hold
     uint32_t* d_rank = nullptr; int32_t* d_pkey = nullptr; int32_t* d_remap = nullptr; size_t remap_cap = 0;  // first update of a session: name ranks, pods' request keys, key -> class
     HandleBuf dl_pin{true}, dl_dev{false};  // the delta's staging: pinned and device, grows, lives with the handle
-    // kai_best_nodes (kai_best_nodes.hpp): pinned staging and device scratch, grow, live with the handle; whether the scratch holds this session's permutation
+    // kai_best_nodes and kai_ordered_nodes (kai_best_nodes.hpp, kai_ordered_nodes.hpp; one pair for both): pinned staging and device scratch, grow, live with the handle; whether the scratch holds this session's permutation
     HandleBuf bn_pin{true}, bn_dev{false}; bool bn_perm_ok = false; int cus = 0;  // (compute units of the device: device_cus)
     // kai_ops_apply (kai_ops_apply.hpp): pinned staging and device scratch, grow, live with the handle; pods the scratch's per-pod arrays hold; caller's node index -> name rank (of this session's permutation)
     HandleBuf oa_pin{true}, oa_dev{false}; size_t oa_pod_cap = 0; std::vector<int32_t> oa_rank; bool oa_rank_ok = false;

@@ -740,6 +740,67 @@ func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipe
 	if len(tasks) == 0 {
 		return nil, nil, true
 	}
+	queries, bitmaps, nRows, known := nodeQueries(pack, tasks, nodeSets, pipelineOnly)
+	if !known {
+		return nil, nil, false
+	}
+	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+	answers := make([]C.kai_node_answer, len(tasks))
+	if rc := C.kai_best_nodes(core, &queries[0], C.int32_t(len(queries)), ptr(bitmaps), C.int32_t(nRows), &answers[0]); rc != 0 {
+		return nil, nil, false
+	}
+	nodes = make([]*node_info.NodeInfo, len(tasks))
+	isPipeline = make([]bool, len(tasks))
+	for i, a := range answers {
+		if a.node >= 0 {
+			nodes[i] = pack.nodes[a.node]
+		}
+		isPipeline[i] = a.is_pipeline != 0
+	}
+	return nodes, isPipeline, true
+}
+
+// OrderedNodes: per task the first k (1 .. C.KAI_ORDERED_MAX_K) entries of Session.OrderedNodesByTask that pass FittingNode, best first, in ONE kai_ordered_nodes
+// call: the list the reference's allocation walks (actions/common/allocate.go), of which BestNodes answers the head.  For a task whose remaining predicates only Go
+// can evaluate (KAI_POD_CPU_FALLBACK: inter-pod affinity, host ports, volumes, DRA) the caller runs its filter down nodes[i] and stops at the first pass, instead
+// of a Go scan of every node when the one best node fails it; "why is this pod pending" tooling reads the runners-up.  The arguments are BestNodes'.
+// nodes[i] holds at most k nodes (fewer: nothing else fits), isPipeline[i][j] belongs to nodes[i][j].  ok = false: as BestNodes, or k out of range.
+func OrderedNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipelineOnly bool, k int) (nodes [][]*node_info.NodeInfo, isPipeline [][]bool, ok bool) {
+	if current == nil || current.pack == nil || current.pack.fallback || len(nodeSets) != len(tasks) || k < 1 || k > C.KAI_ORDERED_MAX_K {
+		return nil, nil, false
+	}
+	pack := current.pack
+	if len(tasks) == 0 {
+		return nil, nil, true
+	}
+	queries, bitmaps, nRows, known := nodeQueries(pack, tasks, nodeSets, pipelineOnly)
+	if !known {
+		return nil, nil, false
+	}
+	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+	answers := make([]C.kai_node_answer, len(tasks)*k)
+	counts := make([]C.int32_t, len(tasks))
+	if rc := C.kai_ordered_nodes(core, &queries[0], C.int32_t(len(queries)), ptr(bitmaps), C.int32_t(nRows), C.int32_t(k), &answers[0], &counts[0]); rc != 0 {
+		return nil, nil, false
+	}
+	nodes = make([][]*node_info.NodeInfo, len(tasks))
+	isPipeline = make([][]bool, len(tasks))
+	for i := range tasks {
+		n := int(counts[i])
+		nodes[i] = make([]*node_info.NodeInfo, n)
+		isPipeline[i] = make([]bool, n)
+		for j := 0; j < n; j++ {
+			a := answers[i*k+j]
+			nodes[i][j] = pack.nodes[a.node]
+			isPipeline[i][j] = a.is_pipeline != 0
+		}
+	}
+	return nodes, isPipeline, true
+}
+
+// nodeQueries: what BestNodes and OrderedNodes send — a kai_node_query per task and the node sets as bitmap rows (nRows of them; tasks that share a slice share a
+// row).  ok = false: a task or node the snapshot does not know.
+func nodeQueries(pack *packedSnapshot, tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipelineOnly bool) (queries []C.kai_node_query, bitmaps []C.uint32_t, nRows int, ok bool) {
 	podOf := make(map[*pod_info.PodInfo]int, len(pack.pods))
 	for i, t := range pack.pods {
 		podOf[t] = i
@@ -754,12 +815,11 @@ func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipe
 		n     int
 	}
 	rows := map[setKey]int{}
-	var bitmaps []C.uint32_t
-	queries := make([]C.kai_node_query, len(tasks))
+	queries = make([]C.kai_node_query, len(tasks))
 	for i, t := range tasks {
 		p, known := podOf[t]
 		if !known {
-			return nil, nil, false
+			return nil, nil, 0, false
 		}
 		queries[i].pod = C.int32_t(p)
 		queries[i].nodeset = -1
@@ -781,7 +841,7 @@ func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipe
 			for _, n := range set {
 				ni, known := nodeOf[n]
 				if !known {
-					return nil, nil, false
+					return nil, nil, 0, false
 				}
 				bitmaps[row*words+ni>>5] |= 1 << (uint(ni) & 31)
 			}
@@ -789,24 +849,10 @@ func BestNodes(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, pipe
 		}
 		queries[i].nodeset = C.int32_t(row)
 	}
-	nRows := 0
 	if words > 0 {
 		nRows = len(bitmaps) / words
 	}
-	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
-	answers := make([]C.kai_node_answer, len(tasks))
-	if rc := C.kai_best_nodes(core, &queries[0], C.int32_t(len(queries)), ptr(bitmaps), C.int32_t(nRows), &answers[0]); rc != 0 {
-		return nil, nil, false
-	}
-	nodes = make([]*node_info.NodeInfo, len(tasks))
-	isPipeline = make([]bool, len(tasks))
-	for i, a := range answers {
-		if a.node >= 0 {
-			nodes[i] = pack.nodes[a.node]
-		}
-		isPipeline[i] = a.is_pipeline != 0
-	}
-	return nodes, isPipeline, true
+	return queries, bitmaps, nRows, true
 }
 
 // AppliedOp is one operation a Go-run action committed through a live Statement: what ApplyOps hands to kai_ops_apply.  Stmt numbers the Statements in commit
