@@ -421,7 +421,7 @@ int action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_cap,
     }
     const auto ta1 = std::chrono::steady_clock::now();
     if (!r.bs.ran) KAI_TRY(action_engine(core, r));
-    if (c.J && !victim) hipLaunchKernelGGL(k_drain, dim3(std::min(2048, (c.J + 255) / 256)), dim3(256), 0, core->stream, c, core->d_slot_queue);
+    if (c.J && !victim) hipLaunchKernelGGL(k_drain, dim3(std::min(2048, (c.J + 255) / 256)), dim3(256), 0, core->stream, c, core->aux.slot_queue);
     HIP_TRY(core, hipGetLastError());
     HIP_TRY(core, hipEventRecord(core->ev1, core->stream));
     HIP_TRY(core, hipMemcpyAsync(&st, KAI_VP(c.st), sizeof(st), hipMemcpyDeviceToHost, core->stream));

@@ -140,10 +140,10 @@ int kai_best_node(kai_core* core, int32_t pod_idx, const uint32_t* nodeset_bitma
         HIP_TRY(core, hipMemcpyAsync(d_bits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, core->stream));
         HIP_TRY(core, hipStreamSynchronize(core->stream));
     }
-    hipLaunchKernelGGL(k_best_node, dim3(1), dim3(WG), 16, core->stream, core->ctx, (int)pod_idx, pipeline_only, core->d_best_out, (const uint32_t*)d_bits);
+    hipLaunchKernelGGL(k_best_node, dim3(1), dim3(WG), 16, core->stream, core->ctx, (int)pod_idx, pipeline_only, core->aux.best_out, (const uint32_t*)d_bits);
     HIP_TRY(core, hipGetLastError());
     int32_t h[2] = {-1, 0};
-    HIP_TRY(core, hipMemcpyAsync(h, core->d_best_out, sizeof h, hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipMemcpyAsync(h, core->aux.best_out, sizeof h, hipMemcpyDeviceToHost, core->stream));
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     if (d_bits) (void)hipFree(d_bits);
     *node_idx_out = h[0] >= 0 ? core->perm[h[0]] : -1;

@@ -5,7 +5,7 @@
 // snapshot holds for every changed pod (status, node, shared-GPU group, flags) without writing the session, so that every refusal is decided before the
 // first write; it also adds up the delta's effect on the count of Releasing / Pipelined pods (wavefront reductions, one atomic per workgroup; the host
 // adjusts the pending pods per request key itself, from the old statuses gathered here).  k_apply_delta then
-// scatters the delta into the baselines kai_session_reset restores (d_status0 / d_node0 / d_group0) and into the nodes' allocatable rows and flags,
+// scatters the delta into the baselines kai_session_reset restores (d_status0 / d_node0 / aux.group0) and into the nodes' allocatable rows and flags,
 // mapping the caller's node indices through the name-rank permutation.  k_class_remap re-labels every pod's scan class when the class table changed.
 // k_apply_rows scatters the rows (RowsView: further arrays of the same buffer) into the QShare baseline, the queues' priorities and min-runtime settings and the jobs'
 // last start times; nothing on the host or the device is derived from those except what kai_session_reset's kernels compute again after every scatter.

@@ -1,5 +1,5 @@
 // kai_handle.hpp — the handle behind the C ABI (struct kai_core) and what every entry point of kai_core.hip shares: the error macros, the buffers that live with the
-// handle (HandleBuf), the session's slab allocator with its upload / fill helpers, the pinned staging of the snapshot's own arrays (UploadStage), free_session.  First of kai_core.hip's own headers.
+// handle (HandleBuf), the session's slab allocator with its upload / fill helpers, the pinned staging of the snapshot's own arrays (UploadStage), the context builder's arena on them (DevArena), free_session.  First of kai_core.hip's own headers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "kai_host_prep.hpp"
+#include "kai_ctx_build.hpp"
 #include "kai_kernels.hpp"
 #include "kai_batch_kernels.hpp"
 #include "kai_batch_driver.hpp"
@@ -59,19 +60,15 @@ struct kai_core {
     HandleBuf pin_buf{true};  // pinned host staging for the operations handed to the caller (grows, lives with the handle)
     char* slab = nullptr; size_t slab_left = 0;
     size_t post_open_max = 0;  // largest slab a request made after kai_session_open needed in this session (trim rule of the next open)
-    // device-only helpers
-    double* d_jsum = nullptr; int32_t* d_slot_queue = nullptr;
-    int32_t *d_lvl_off = nullptr, *d_lvl_parents = nullptr; int n_levels = 0; std::vector<int32_t> h_lvl_off;
-    int32_t *d_h_off = nullptr, *d_h_nodes = nullptr; int n_heights = 0;  // queues by height (leaf = 0), for the usage roll-up
-    double *d_weight = nullptr, *d_rem_amt = nullptr; uint8_t* d_rem_has = nullptr;
-    int32_t* d_best_out = nullptr;
+    OpenAux aux;  // the open's arrays that are no part of the context (kai_ctx_build.hpp): arguments of the session-open kernels, k_drain, k_best_node
+    int n_levels = 0; std::vector<int32_t> h_lvl_off; int n_heights = 0;  // fair-share levels (aux.lvl_off on the host), heights of the queue tree
     int32_t *d_status0 = nullptr, *d_node0 = nullptr; QShare* d_shares0 = nullptr;  // HBM-resident initial state for kai_session_reset
     std::vector<int32_t> perm;  // engine node index (= name rank) → caller's node index
     kai_action_stats stats{};
     HostPrep::BatchShape shape;  // batch path of the allocate action (kai_batch.hpp)
     int world = 1, rank = 0, shard_k = 0; kai_allgather_fn ag_fn = nullptr; void* ag_user = nullptr;  // node-axis sharding over the GPUs of one node (kai_shard_attach)
     void* rccl_comm = nullptr;  // the library's own communicator (kai_shard_attach_rccl): the exchange is an ncclAllGather on `stream`, no host round trip
-    bool shared = false; int32_t* d_group0 = nullptr; int32_t next_group0 = 0; int32_t *d_np_off = nullptr, *d_np_pods = nullptr;  // shared GPUs: initial groups, each node's active pods in UID order
+    bool shared = false; int32_t next_group0 = 0;  // shared GPUs in the session; the first group id a cycle may open (kai_session_reset)
     hipEvent_t bev[4] = {nullptr, nullptr, nullptr, nullptr};
     // rounds without the host (kai_batch_driver.hpp): per slot the round's phase events (plan start, fill start, fill end, apply end), the event behind its RoundCtl copy, the pinned copy
     hipEvent_t rev[KB_ROUND_SLOTS][5] = {}; HandleBuf rpin{true}; bool rev_ready = false;
@@ -174,6 +171,12 @@ template <class F, class T> int dupload_f(kai_core* core, F& field, const T* hos
     else HIP_TRY(core, hipMemsetAsync(KAI_VP(field), 0, sizeof(T), core->stream));  // (an empty array is one element nobody reads: zeros rather than what the slab held before)
     return KAI_OK;
 }
+template <class F, class S> int dcopy_f(kai_core* core, F& field, S src, size_t n) {  // the array allocated and filled from device memory
+    static_assert(sizeof(*field) == sizeof(*src), "element size");
+    KAI_TRY(dalloc_f(core, field, n));
+    if (n) HIP_TRY(core, hipMemcpyAsync(KAI_VP(field), KAI_VP(src), n * sizeof(*field), hipMemcpyDeviceToDevice, core->stream));
+    return KAI_OK;
+}
 // The snapshot's own arrays (nothing the host preparation derives) go up FIRST and from pinned memory: add() allocates the device array, flush() copies the host arrays into the
 // handle's pinned staging buffer on the host's cores and enqueues one DMA per array — which then runs while kai_session_open's host preparation (milliseconds of loops over the same
 // pods and jobs) keeps the cores busy.  hipMemcpyAsync from the caller's pageable arrays, as every other upload of the open is made, stages through the runtime's own bounce buffers on
@@ -203,6 +206,18 @@ struct UploadStage {
         segs.clear(); total = 0;
         return KAI_OK;
     }
+};
+// kai_ctx_build.hpp's arena on the session's slabs: the helpers above, the first failure kept
+struct DevArena {
+    kai_core* core; UploadStage up{core}; int rc = KAI_OK;
+    template <class F> void alloc(F& field, size_t n) { if (!rc) rc = dalloc_f(core, field, n); }
+    template <class F> void fill(F& field, size_t n, int byte) { if (!rc) rc = dfill_f(core, field, n, byte); }
+    template <class F> void zero(F& field, size_t n) { fill(field, n, 0); }
+    template <class F, class T> void upload(F& field, const T* host, size_t n) { if (!rc) rc = dupload_f(core, field, host, n); }
+    template <class F, class T> void stage(F& field, const T* host, size_t n) { if (!rc) rc = up.add(field, host, n); }
+    int flush() { if (!rc) rc = up.flush(); return rc; }
+    template <class F, class S> void copy_of(F& field, S src, size_t n) { if (!rc) rc = dcopy_f(core, field, src, n); }
+    int status() const { return rc; }
 };
 void free_session(kai_core* core, bool release = false) {
     // the slabs stay with the handle for the next session (dalloc takes them back); kai_core_destroy releases them

@@ -69,7 +69,7 @@ struct SessionUpdate {
         HIP_TRY(core, hipMemsetAsync(d_cnt, 0, 256, core->stream));
         HIP_TRY(core, hipMemcpyAsync(dv, pin, L.o_out, hipMemcpyHostToDevice, core->stream));
         if (NP) hipLaunchKernelGGL(k_delta_gather, dim3((NP + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, v, (const int32_t*)core->d_status0, (const int32_t*)core->d_node0,
-                                   (const int32_t*)core->d_group0, (const uint32_t*)KAI_VP(c.p_flags), d_out, d_cnt);
+                                   (const int32_t*)core->aux.group0, (const uint32_t*)KAI_VP(c.p_flags), d_out, d_cnt);
         HIP_TRY(core, hipGetLastError());
         HIP_TRY(core, hipMemcpyAsync(pin + L.o_out, d_out, L.o_cnt + 256 - L.o_out, hipMemcpyDeviceToHost, core->stream));
         HIP_TRY(core, hipStreamSynchronize(core->stream));
@@ -188,7 +188,7 @@ struct SessionUpdate {
                       HIP_TRY(core, hipMemcpyAsync(dv + L.o_f64, h64, (size_t)R * NX * 8, hipMemcpyHostToDevice, core->stream)); }
         }
         v.node = dnode; v.node_flags = dflags; v.n_nodes = NX;
-        if (NP + NX) hipLaunchKernelGGL(k_apply_delta, dim3((NP + NX + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, v, core->d_status0, core->d_node0, core->d_group0,
+        if (NP + NX) hipLaunchKernelGGL(k_apply_delta, dim3((NP + NX + KD_TB - 1) / KD_TB), dim3(KD_TB), 0, core->stream, v, core->d_status0, core->d_node0, core->aux.group0,
                                         (double*)KAI_VP(c.n_alloc), (uint32_t*)KAI_VP(c.n_flags));
         HIP_TRY(core, hipGetLastError());
         if (NQ + NJ) {
@@ -234,9 +234,9 @@ struct SessionUpdate {
             for (int n = 0; n < N; n++) np_off[(size_t)n + 1] = np_off[(size_t)n] + (int32_t)core->np_lists[(size_t)n].size();
             np_pods.reserve((size_t)np_off[(size_t)N]);
             for (int n = 0; n < N; n++) for (const auto& x : core->np_lists[(size_t)n]) np_pods.push_back(x.second);
-            if (np_pods.size() > core->np_cap) { int32_t* t = nullptr; KAI_TRY(dalloc(core, &t, np_pods.size())); core->d_np_pods = t; core->np_cap = np_pods.size(); }
-            HIP_TRY(core, hipMemcpyAsync(core->d_np_off, np_off.data(), np_off.size() * 4, hipMemcpyHostToDevice, core->stream));
-            if (!np_pods.empty()) HIP_TRY(core, hipMemcpyAsync(core->d_np_pods, np_pods.data(), np_pods.size() * 4, hipMemcpyHostToDevice, core->stream));
+            if (np_pods.size() > core->np_cap) { int32_t* t = nullptr; KAI_TRY(dalloc(core, &t, np_pods.size())); core->aux.np_pods = t; core->np_cap = np_pods.size(); }
+            HIP_TRY(core, hipMemcpyAsync(core->aux.np_off, np_off.data(), np_off.size() * 4, hipMemcpyHostToDevice, core->stream));
+            if (!np_pods.empty()) HIP_TRY(core, hipMemcpyAsync(core->aux.np_pods, np_pods.data(), np_pods.size() * 4, hipMemcpyHostToDevice, core->stream));
             HIP_TRY(core, hipStreamSynchronize(core->stream));
         }
         // the context's scalars as the open sets them from the snapshot

@@ -69,6 +69,18 @@ extern "C" int kai_hostsim_run(const kai_config* cfg, const kai_snapshot_soa* s,
     return KAI_OK;
 }
 
+// what the open's builder (kai_ctx_build.hpp) put into every array of a session's context, as the lines kai_session_open prints under KAI_OPEN_DIGEST (tests/test_open_uploads.py
+// holds them against the library's): the text into out, its length into *n also where out is NULL or too small
+extern "C" int kai_hostsim_open_digest(const kai_config* cfg, const kai_snapshot_soa* s, char* out, int64_t cap, int64_t* n) {
+    SimSession ss; std::string text; ss.digest_out = &text;
+    if (int rc = ss.open(cfg, s, 1)) return rc;
+    if (n) *n = (int64_t)text.size();
+    if (!out) return KAI_OK;
+    if ((int64_t)text.size() > cap) return KAI_ERR_CAPACITY;
+    std::memcpy(out, text.data(), text.size());
+    return KAI_OK;
+}
+
 // ---- kai_victim_shard.hpp on its own (tests/test_dist_gloo.py::test_wave_exchange_protocol): R ranks in one process, the "all-gather" a memcpy between their send buffers.
 // mode 0: random waves — every rank must end with the identical merged wave, equal to what one rank running every simulation would hold (returns 0, or the failing check).
 // mode 1: rank `arg` leaves the protocol (its closing message with the fault flag) while the others are in a wave — they must see the fault, skip their own closing

@@ -17,6 +17,7 @@ static int g_dom_lanes_min = std::getenv("KAI_HOSTSIM_DOM_MIN") ? std::atoi(std:
 #include <vector>
 
 #include "../../kai-scheduler_amd/csrc/kai_host_prep.hpp"
+#include "../../kai-scheduler_amd/csrc/kai_ctx_build.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_batch_kernels.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_batch_driver.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_victim_shard.hpp"
@@ -298,11 +299,27 @@ template <class T> T* own(std::vector<std::vector<char>>& pool, size_t n) {
     pool.emplace_back(std::max<size_t>(n, 1) * sizeof(T), 0);
     return reinterpret_cast<T*>(pool.back().data());
 }
-template <class T> const T* copy(std::vector<std::vector<char>>& pool, const T* src, size_t n) {
-    T* d = own<T>(pool, n);
-    if (n && src) std::memcpy(d, src, n * sizeof(T));
-    return d;
-}
+// kai_ctx_build.hpp's arena on host memory: one vector per array (an overrun stays visible to a sanitizer), every array of the context recorded as kai_core::AllocRec
+// records it, and an array that is allocated WITHOUT being written filled with a byte that is neither 0 nor -1 — so that a read of it shows up here, where the
+// library's slab holds whatever the last session left
+struct SimArena {
+    static constexpr int kPoison = 0x5A;  // (an int32 of it is a large positive number: an index or a group id that cannot go unnoticed)
+    struct Rec { size_t field_off; char* base; size_t bytes, live; };  // (live: without the one element of an empty array, which nobody reads)
+    std::vector<std::vector<char>>& pool; const KaiCtx& c; std::vector<Rec>* recs = nullptr;
+    template <class F> char* take(F& field, size_t n, int byte) {
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(*field);
+        pool.emplace_back(bytes, (char)byte); char* p = pool.back().data(); field = (F)p;
+        const char* fp = reinterpret_cast<const char*>(&field); const char* c0 = reinterpret_cast<const char*>(&c);
+        if (recs && fp >= c0 && fp + sizeof(void*) <= c0 + sizeof(KaiCtx)) recs->push_back({(size_t)(fp - c0), p, bytes, n * sizeof(*field)});
+        return p;
+    }
+    template <class F> void alloc(F& field, size_t n) { take(field, n, kPoison); }
+    template <class F> void fill(F& field, size_t n, int byte) { take(field, n, byte); } template <class F> void zero(F& field, size_t n) { take(field, n, 0); }
+    template <class F, class T> void upload(F& field, const T* host, size_t n) { static_assert(sizeof(*field) == sizeof(T), "element size"); char* p = take(field, n, 0); if (n) std::memcpy(p, host, n * sizeof(T)); }
+    template <class F, class T> void stage(F& field, const T* host, size_t n) { upload(field, host, n); } int flush() { return 0; }
+    template <class F, class S> void copy_of(F& field, S src, size_t n) { static_assert(sizeof(*field) == sizeof(*src), "element size"); char* p = take(field, n, kPoison); if (n) std::memcpy(p, src, n * sizeof(*field)); }
+    int status() const { return 0; }
+};
 
 // the switches of the next sessions, written by the kai_hostsim_set_* exports (host_sim.cpp), and what the last run left for kai_hostsim_last_* / kai_hostsim_multi_stats
 // node-sharded run (tests/test_dist_gloo.py): rank / world / offers per class and the all-gather of the test's process group
@@ -319,9 +336,11 @@ struct SimSession {
     const kai_config* cfg = nullptr; const kai_snapshot_soa* s = nullptr;
     SharedPods sp;  // shared GPUs in the engine: one GPU memory size for the whole cluster (the queue-capacity step stays node independent)
     HostPrep prep; bool shared = false; int n_actions_total = 1; bool batch_path = true;
-    std::vector<std::vector<char>> pool; KaiCtx c{};
+    std::vector<std::vector<char>> pool; KaiCtx c{}; OpenAux aux;  // (aux: the arguments of the real open kernels; the serial twins below read prep instead)
+    std::vector<SimArena::Rec> recs;  // every array of the context, as kai_core::allocs lists them
+    std::string* digest_out = nullptr;  // set before open: what the builder put into every array, before the serial twins of the open kernels run — the lines kai_session_open prints under KAI_OPEN_DIGEST
     HostBackend be; std::optional<Engine<HostBackend>> eng;  // the one engine that lives across the session's actions
-    struct Rep { std::vector<std::vector<char>> pool; KaiCtx c{}; };
+    struct Rep { std::vector<std::vector<char>> pool; KaiCtx c{}; OpenAux aux; };
     std::vector<Rep> reps;  // further engines of a victim action: replicas of the context, of identical layout
     bool index_stale = false; int64_t batch_rounds = 0, batch_actions = 0, bucket_actions = 0, counts_actions = 0, levels_actions = 0;
     std::chrono::steady_clock::time_point t0;  // (elapsed_ms: from the open's math on)
@@ -335,116 +354,42 @@ struct SimSession {
         if (const char* e = std::getenv("KAI_HOSTSIM_MW")) { const int v = std::atoi(e); if (v > 0) g_mw_world = v > KAI_MW_MAX ? KAI_MW_MAX : v; }
         if (!sp.build(*cfg, s)) return KAI_ERR_UNSUPPORTED;
         shared = sp.any;
-        if (!lean_shared_pods_hold()) return KAI_ERR_STATE;
         std::string err; prep.shared_pods = sp.any ? &sp : nullptr;
         if (prep.build(*cfg, s, err)) return KAI_ERR_INVALID_ARG;
-        if (!default_tables_hold()) return KAI_ERR_STATE;
-        for (int p = 0; p < s->n_pods; p++)  // NodeInfo.LegacyMIGTasks (node_info.go:407-409): a node that holds a legacy MIG task takes no MIG request
-            if (s->pod_flags && (s->pod_flags[p] & KAI_POD_LEGACY_MIG) && prep.pod_node[p] >= 0 && (s->pod_status[p] & (KAI_POD_ALLOCATED | KAI_POD_PIPELINED | KAI_POD_BINDING | KAI_POD_BOUND | KAI_POD_RUNNING | KAI_POD_RELEASING))) prep.node_flags[prep.pod_node[p]] |= KAI_NODE_LEGACY_MIG_I;
-        if (int rc = alloc_ctx(pool, c)) return rc;
+        if (s->pod_flags) { std::vector<int32_t> cnt; flag_legacy_mig_nodes(s, prep, cnt); }
+        if (int rc = build_ctx(pool, c, aux, &recs)) return rc;
+        if (!lean_equals_full()) return KAI_ERR_STATE;
+        if (digest_out) for (const SimArena::Rec& a : recs) {
+            uint64_t f = 1469598103934665603ull; for (size_t i = 0; i < a.bytes; i++) { f ^= (unsigned char)a.base[i]; f *= 1099511628211ull; }
+            char ln[96]; std::snprintf(ln, sizeof ln, "kai open digest: field %zu bytes %zu fnv %016llx\n", a.field_off, a.bytes, (unsigned long long)f); *digest_out += ln;
+        }
         t0 = std::chrono::steady_clock::now();
         if (int rc = derive_open_state()) return rc;
         eng.emplace(c, be);
         return KAI_OK;
     }
-    // lean_shared_pods_hold: kai_session_open (kai_session_open.hpp open_shared_gpus) does not SEND the per-pod arrays of the shared-GPU model for a snapshot without shared-GPU requests and MIG rows — it
-    // writes the constants they hold on the device.  That they hold exactly those constants is checked here, on every snapshot the CPU suite runs.
-    bool lean_shared_pods_hold() const {
-        const int P = s->n_pods;
-        if (!sp.on) for (int p = 0; p < P; p++) {
-            const double g = s->pod_req[(size_t)KAI_RES_GPU * P + p];
-            const bool same = std::memcmp(&sp.acc_gpu[p], &g, 8) == 0 && std::memcmp(&sp.pend_gpu[p], &g, 8) == 0 && std::memcmp(&sp.quota_gpu[p], &g, 8) == 0;
-            const double z = 0.0;
-            if (!same || sp.shared[p] != 0 || sp.mem[p] != 0 || sp.gmem[p] != 0 || std::memcmp(&sp.mig_q[p], &z, 8) != 0) { std::fprintf(stderr, "lean_shared_pods_hold: pod %d breaks the constants kai_session_open writes on the device\n", p); return false; }
-        }
-        return true;
-    }
-    // the other constants kai_session_open writes on the device instead of sending them (kai_session_open.hpp: prep.groups_default, !prep.any_nominated) — checked on every snapshot the CPU suite runs
-    bool default_tables_hold() const {
-        const int P = s->n_pods, S = s->n_podsets, J = s->n_jobs;
-        bool ok = true;
-        if (!prep.any_nominated) for (int p = 0; p < P; p++) ok = ok && prep.pod_nominated[p] == -1;
-        if (prep.groups_default) {
-            ok = ok && prep.G == J && (int)prep.g_job.size() == J && (int)prep.g_parent.size() == J && (int)prep.g_topo.size() == J && (int)prep.g_req.size() == J && (int)prep.g_pref.size() == J && (int)prep.g_name_rank.size() == J
-                    && (int)prep.g_child_off.size() == J + 1 && (int)prep.j_has_topology.size() == std::max(J, 1) && (int)prep.s_group.size() == S && (int)prep.s_topo.size() == S && (int)prep.s_req.size() == S && (int)prep.s_pref.size() == S;
-            for (int j = 0; j < J && ok; j++) ok = prep.g_parent[j] == -1 && prep.g_topo[j] == -1 && prep.g_req[j] == -1 && prep.g_pref[j] == -1 && prep.g_name_rank[j] == 0 && prep.g_child_off[j] == 0 && prep.j_has_topology[j] == 0;
-            ok = ok && prep.g_child_off[J] == 0 && prep.j_has_topology[0] == 0;
-            for (int k = 0; k < S && ok; k++) ok = prep.s_group[k] == s->podset_job[k] && prep.s_topo[k] == -1 && prep.s_req[k] == -1 && prep.s_pref[k] == -1;
-        }
-        if (!ok) std::fprintf(stderr, "host_sim: HostPrep's default tables differ from the constants kai_session_open writes on the device\n");
+    // kai_session_open does not SEND what a snapshot holds as constants (kai_ctx_build.hpp: the shared-GPU model's per-pod arrays without shared-GPU requests and MIG rows, the
+    // identity tables of a snapshot without sub-group trees, "no nominated node") — it writes them where they are read.  That they are what would have been sent is checked here on
+    // every snapshot the CPU suite runs: the context built the other way (with / without KAI_OPEN_FULL_UPLOADS) is bytewise equal to this session's
+    bool lean_equals_full() const {
+        std::vector<std::vector<char>> pool2; KaiCtx c2{}; OpenAux aux2; std::vector<SimArena::Rec> recs2;
+        bool ok = build_arrays(pool2, c2, aux2, &recs2, !full_uploads()) == 0 && recs2.size() == recs.size();
+        for (size_t i = 0; i < recs.size() && ok; i++) ok = recs2[i].field_off == recs[i].field_off && recs2[i].bytes == recs[i].bytes && std::memcmp(recs2[i].base, recs[i].base, recs[i].live) == 0;
+        if (!ok) std::fprintf(stderr, "host_sim: the constants kai_session_open writes on the device differ from what KAI_OPEN_FULL_UPLOADS sends\n");
         return ok;
     }
-    // every array of the context: what derive_open_state works on, then what the actions add (solver scratch, batch path); a member so that further engines of a victim action get replicas of identical layout
-    int alloc_ctx(std::vector<std::vector<char>>& pool, KaiCtx& c) const {
-        const int N = s->n_nodes, P = s->n_pods, S = s->n_podsets, J = s->n_jobs, Q = s->n_queues, R = s->n_res, n_actions = n_actions_total;
-        c.N = N; c.P = P; c.S = S; c.J = J; c.Q = Q; c.R = R; c.n_pod_classes = std::max(1, s->n_pod_classes); c.n_node_classes = std::max(1, s->n_node_classes);
-        c.plugins = cfg->plugins; c.gpu_strategy = cfg->gpu_strategy; c.cpu_strategy = cfg->cpu_strategy; c.restrict_nodes = cfg->restrict_node_scheduling;
-        c.k_value = cfg->k_value <= 0.0 ? 0.0 : cfg->k_value;
-        std::vector<int32_t> zerop(P, 0); std::vector<uint32_t> zeropu(P, 0); uint8_t one = 1;
-        c.n_alloc = copy(pool, prep.node_alloc.data(), (size_t)R * N); c.n_flags = const_cast<uint32_t*>(copy(pool, prep.node_flags.data(), N));
-        c.n_gpu_count = copy(pool, prep.node_gpu_count.data(), N); c.n_class = copy(pool, prep.node_class.data(), N);
-        c.p_req = copy(pool, s->pod_req, (size_t)R * P); c.p_job = copy(pool, s->pod_job, P); c.p_podset = copy(pool, s->pod_podset, P);
-        c.p_flags = copy(pool, s->pod_flags ? s->pod_flags : zeropu.data(), P); c.p_class = copy(pool, s->pod_class ? s->pod_class : zerop.data(), P);
-        c.p_nominated = copy(pool, prep.pod_nominated.data(), P); c.p_scls = copy(pool, prep.pod_scls.data(), P);
-        c.s_job = copy(pool, s->podset_job, S); c.s_min = copy(pool, s->podset_min_available, S); c.s_name_rank = copy(pool, s->podset_name_rank, S);
-        c.j_queue = copy(pool, s->job_queue, J); c.j_prio = copy(pool, s->job_priority, J); c.j_preempt = copy(pool, s->job_preemptible, J);
-        c.j_created = copy(pool, s->job_created_ns, J); c.j_uid_rank = copy(pool, s->job_uid_rank, J); c.j_first_pod = copy(pool, s->job_first_pod, J);
-        c.j_n_pods = copy(pool, s->job_n_pods, J); c.j_first_ps = copy(pool, s->job_first_podset, J); c.j_n_ps = copy(pool, s->job_n_podsets, J);
-        c.q_parent = copy(pool, s->queue_parent, Q); c.q_prio = copy(pool, s->queue_priority, Q); c.q_created = copy(pool, s->queue_created_ns, Q); c.q_uid_rank = copy(pool, s->queue_uid_rank, Q);
-        if (s->class_fit && s->n_pod_classes > 0 && s->n_node_classes > 0) c.class_fit = copy(pool, s->class_fit, (size_t)s->n_pod_classes * s->n_node_classes);
-        else c.class_fit = copy(pool, &one, 1);
-        c.j_pods_sorted = copy(pool, prep.sorted.data(), P); c.q_child_off = copy(pool, prep.child_off.data(), Q + 2); c.q_children = copy(pool, prep.children.data(), std::max(Q, 1));
-        c.q_job_off = copy(pool, prep.job_off.data(), Q + 1); c.jobs_static = copy(pool, prep.jobs_static.data(), std::max(J, 1)); c.q_depth_order = copy(pool, prep.depth_order.data(), Q);
-        c.C = (int)prep.classes.size(); c.NB = (N + KAI_BLOCK - 1) / KAI_BLOCK; c.NSB = (c.NB + 63) / 64; c.use_index = c.C > 0; c.all_tracked = prep.all_tracked; c.fast_ok = prep.fast_ok; c.exact_sums = prep.exact_sums;
-        if (shared || sp.mig) { c.all_tracked = 0; const char* e = std::getenv("KAI_SHARED_INDEX"); const int lvl = e ? std::atoi(e) : 2; if (sp.mig || lvl == 0) c.use_index = 0; if (sp.mig || lvl < 2) c.fast_ok = 0; }  // as kai_session_open: fractions in no class, the others indexed with the gpusharingorder bit
-        { int d = cfg->queue_depth[KAI_ACTION_ALLOCATE]; c.queue_depth = d > 0 ? d : 0; }
-        c.cls = copy(pool, prep.classes.data(), prep.classes.size());
-        c.T = prep.T; c.TL = prep.TL; c.D = prep.D; c.G = prep.G; c.W = (N + 31) / 32;
-        { const size_t DT = (size_t)prep.D + prep.T;
-          c.topo_level_off = copy(pool, prep.topo_level_off.data(), prep.topo_level_off.size()); c.node_domain = copy(pool, prep.node_domain.data(), prep.node_domain.size());
-          c.dom_level = copy(pool, prep.dom_level.data(), prep.dom_level.size()); c.dom_topo = copy(pool, prep.dom_topo.data(), prep.dom_topo.size());
-          c.dom_parent = copy(pool, prep.dom_parent.data(), prep.dom_parent.size()); c.dom_id_rank = copy(pool, prep.dom_id_rank.data(), prep.dom_id_rank.size());
-          c.dom_child_off = copy(pool, prep.dom_child_off.data(), prep.dom_child_off.size()); c.dom_children = const_cast<int32_t*>(copy(pool, prep.dom_children.data(), prep.dom_children.size()));
-          c.dom_alloc_pods = own<int32_t>(pool, DT); c.dom_free = own<double>(pool, DT * KAI_MAX_RES); c.dom_tmp = own<int32_t>(pool, 3 * DT + 4); c.dom_ratio = own<double>(pool, DT); c.dom_key = own<int64_t>(pool, 2 * DT);
-          c.ns_bits = own<uint32_t>(pool, (size_t)KAI_TDEPTH * std::max(c.W, 1)); c.ns_sets = own<int32_t>(pool, (size_t)KAI_TDEPTH * (DT + 1));
-          c.sg_score = own<double>(pool, (size_t)KAI_TKEYS * std::max<size_t>(DT, 1)); c.sg_key = own<int32_t>(pool, KAI_TKEYS); c.sg_row = own<int32_t>(pool, KAI_TKEYS); }
-        c.g_job = copy(pool, prep.g_job.data(), prep.g_job.size()); c.g_parent = copy(pool, prep.g_parent.data(), prep.g_parent.size()); c.g_name_rank = copy(pool, prep.g_name_rank.data(), prep.g_name_rank.size());
-        c.g_topo = copy(pool, prep.g_topo.data(), prep.g_topo.size()); c.g_req = copy(pool, prep.g_req.data(), prep.g_req.size()); c.g_pref = copy(pool, prep.g_pref.data(), prep.g_pref.size());
-        c.j_root_group = copy(pool, prep.j_root_group.data(), prep.j_root_group.size()); c.g_child_off = copy(pool, prep.g_child_off.data(), prep.g_child_off.size()); c.g_children = copy(pool, prep.g_children.data(), prep.g_children.size());
-        c.s_group = copy(pool, prep.s_group.data(), prep.s_group.size()); c.s_topo = copy(pool, prep.s_topo.data(), prep.s_topo.size()); c.s_req = copy(pool, prep.s_req.data(), prep.s_req.size());
-        c.s_pref = copy(pool, prep.s_pref.data(), prep.s_pref.size()); c.j_has_topology = copy(pool, prep.j_has_topology.data(), prep.j_has_topology.size());
-        c.sum1_key = own<uint64_t>(pool, (size_t)std::max(c.C, 1) * std::max(c.NB, 1)); c.sum1_node = own<int32_t>(pool, (size_t)std::max(c.C, 1) * std::max(c.NB, 1));
-        c.n_idle = const_cast<double*>(copy(pool, prep.node_alloc.data(), (size_t)R * N)); c.n_rel = own<double>(pool, (size_t)R * N); c.n_used = own<double>(pool, (size_t)R * N);
-        c.p_status = const_cast<int32_t*>(copy(pool, s->pod_status, P)); c.p_node = const_cast<int32_t*>(copy(pool, prep.pod_node.data(), P));
-        c.p_on_node = own<int32_t>(pool, P); c.p_on_node_status = own<int32_t>(pool, P); c.p_virtual = own<uint8_t>(pool, P); c.p_accepted = own<uint8_t>(pool, P);
-        {   // shared-GPU tables (KaiCtx, KAI_SHARED_GPUS): nodes in name-rank order like every other node array
-            c.shared_on = shared ? 1 : 0;
-            double* por = own<double>(pool, P); int32_t* grp = own<int32_t>(pool, P); int32_t* ogrp = own<int32_t>(pool, P); int64_t* gm = own<int64_t>(pool, N);
-            int32_t next_new = KAI_NEW_GROUP;
-            for (int p = 0; p < P; p++) { por[p] = s->pod_gpu_portion ? s->pod_gpu_portion[p] : 0.0; grp[p] = (s->pod_gpu_group && sp.shared[p]) ? s->pod_gpu_group[p] : -1; ogrp[p] = -1; if (grp[p] >= next_new) next_new = grp[p] + 1; }
-            c.p_shared = copy(pool, sp.shared.data(), P); c.p_mem = copy(pool, sp.mem.data(), P); c.p_gmem = copy(pool, sp.gmem.data(), P); c.p_acc_gpu = copy(pool, sp.acc_gpu.data(), P); c.p_pend_gpu = copy(pool, sp.pend_gpu.data(), P);
-            c.p_quota_gpu = copy(pool, sp.quota_gpu.data(), P); c.p_mig_q = copy(pool, sp.mig_q.data(), P); c.p_kind = copy(pool, sp.kind.data(), P); c.quota_on = sp.on ? 1 : 0; c.mig_on = sp.mig ? 1 : 0;
-            for (int r = 0; r < KAI_MAX_RES; r++) { c.res_mig_g[r] = sp.mig_g[r]; c.res_mig_m[r] = sp.mig_m[r]; }
-            for (int n = 0; n < N; n++) gm[n] = s->node_gpu_memory ? s->node_gpu_memory[prep.perm[n]] : 100;
-            c.p_portion = por; c.p_group = grp; c.p_on_group = ogrp; c.n_gpu_mem = gm;
-            c.ng_id = own<int32_t>(pool, (size_t)N * KAI_GMAX); for (size_t i = 0; i < (size_t)N * KAI_GMAX; i++) c.ng_id[i] = -1;
-            c.ng_used = own<int64_t>(pool, (size_t)N * KAI_GMAX); c.ng_rel = own<int64_t>(pool, (size_t)N * KAI_GMAX); c.ng_alloc = own<int64_t>(pool, (size_t)N * KAI_GMAX);
-            c.ng_mark = own<uint32_t>(pool, N); c.ng_has_alloc = own<uint32_t>(pool, N);
-            c.next_new_group = own<int32_t>(pool, 1); c.next_new_group[0] = next_new;
-        }
-        c.s_active_alloc = own<int32_t>(pool, S); c.s_active_used = own<int32_t>(pool, S); c.s_alive = own<int32_t>(pool, S); c.s_gated = own<int32_t>(pool, S); c.s_pipelined = own<int32_t>(pool, S);
-        c.j_n_pending = own<int32_t>(pool, J); c.j_tta_valid = own<int32_t>(pool, J); c.j_tta_n = own<int32_t>(pool, J); c.tta = own<int32_t>(pool, P);
-        c.j_tta_res = own<double>(pool, (size_t)4 * J); c.j_allocated = own<double>(pool, (size_t)4 * J);
-        c.lq_sorted = own<int32_t>(pool, J); c.lq_side = own<int32_t>(pool, J); c.lq_cur = own<int32_t>(pool, Q); c.lq_end = own<int32_t>(pool, Q); c.lq_side_len = own<int32_t>(pool, Q); c.j_state = own<uint8_t>(pool, J);
-        c.qheap = own<int32_t>(pool, Q + 1); c.root_heap = own<int32_t>(pool, Q + 1); c.qn = own<QNode>(pool, Q + 1);
-        c.ops_cap = 4 * P + 64; c.ops = own<StmtOp>(pool, c.ops_cap); c.out_cap = ((int64_t)2 * P + 64) * (n_actions > 0 ? n_actions : 1); c.out_ops = own<kai_op>(pool, c.out_cap);  // the library gives every action its own 2P + 64; this harness keeps one list for the whole cycle
-        c.scratch = own<int32_t>(pool, (size_t)P + 64); c.st = own<EngineState>(pool, 1);
-        c.q_share = const_cast<QShare*>(copy(pool, prep.shares.data(), prep.shares.size()));
-        c.use_signatures = cfg->use_scheduling_signatures ? 1 : 0; c.j_signature = s->job_signature ? copy(pool, s->job_signature, J) : nullptr;
-        c.j_last_start = s->job_last_start_ns ? copy(pool, s->job_last_start_ns, J) : nullptr; c.q_preempt_mr = s->queue_preempt_min_runtime_ns ? copy(pool, s->queue_preempt_min_runtime_ns, Q) : nullptr;
-        c.q_reclaim_mr = s->queue_reclaim_min_runtime_ns ? copy(pool, s->queue_reclaim_min_runtime_ns, Q) : nullptr;
-        c.now_ns = cfg->now_ns; c.def_preempt_mr = cfg->default_preempt_min_runtime_ns; c.def_reclaim_mr = cfg->default_reclaim_min_runtime_ns; c.reclaim_method = cfg->reclaim_resolve_method;
-        c.max_consolidation_preemptees = cfg->max_consolidation_preemptees; c.allow_consolidating_reclaim = cfg->allow_consolidating_reclaim; c.saturation_multiplier = cfg->reclaimer_saturation_multiplier;
+    static bool full_uploads() { return std::getenv("KAI_OPEN_FULL_UPLOADS") != nullptr; }
+    // the context's arrays on `pool` by the library's builder (kai_ctx_build.hpp), ONE out_ops list for the whole cycle (the builder's out_lists)
+    int build_arrays(std::vector<std::vector<char>>& pool, KaiCtx& c, OpenAux& aux, std::vector<SimArena::Rec>* recs, bool full) const {
+        SimArena arena{pool, c, recs}; CtxBuildOut built;
+        ctx_scalars(c, *cfg, s);
+        if (int rc = ctx_stage_snapshot(arena, c, s)) return rc;
+        return ctx_build(arena, c, aux, CtxBuildIn{*cfg, s, prep, sp, full, n_actions_total}, built);
+    }
+    // ... then what only this harness does — the solver scratch bound at once, the batch path's pools; a member so that further engines of a victim action get replicas of identical layout
+    int build_ctx(std::vector<std::vector<char>>& pool, KaiCtx& c, OpenAux& aux, std::vector<SimArena::Rec>* recs = nullptr) const {
+        if (int rc = build_arrays(pool, c, aux, recs, full_uploads())) return rc;
+        const int N = c.N, P = c.P, S = c.S, J = c.J, Q = c.Q;
         { size_t bytes = solver_scratch_bytes(N, P, S, J, Q, c.W, c.D + c.T, c.TL, c.G); char* base = own<char>(pool, bytes); solver_scratch_bind(c.sv, base, N, P, S, J, Q, c.W, c.D + c.T, c.TL, c.G); for (int i = 0; i <= c.sv.xr_mask; i++) c.sv.xr_key[i] = -1; c.sv.xr_group = own<int32_t>(pool, (size_t)c.sv.xr_mask + 1); }
         if (int rc = batch_bind(c, prep, [&](size_t bytes) { return (void*)own<char>(pool, bytes); }, [&](void* d, const void* h, size_t n) { std::memcpy(d, h, n); return 0; }, g_sh_world, g_sh_rank, g_sh_k)) return rc;
         if (shared || !batch_path || std::getenv("KAI_HOSTSIM_NO_BATCH")) c.bt.enabled = 0;
@@ -456,6 +401,7 @@ struct SimSession {
         const int N = c.N, P = c.P, R = c.R;
         std::vector<int> acct(P); for (int p = 0; p < P; p++) acct[p] = p;
         if (shared) std::sort(acct.begin(), acct.end(), [&](int a, int b) { return s->pod_uid_rank[a] < s->pod_uid_rank[b]; });  // AddTasksToNode order of the fixtures (nodes_fake/nodes.go:289-302): the shared-GPU guards are order sensitive
+        if (shared) std::memset(c.ng_id, 0xFF, sizeof(int32_t) * (size_t)N * KAI_GMAX);  // as launch_open_kernels resets the group tables
         for (int p = 0; p < P; p++) c.p_on_node[p] = -1;
         for (int pi = 0; pi < P; pi++) {  // k_node_accounting
             const int p = acct[pi];
@@ -588,7 +534,7 @@ struct SimSession {
         c.mw_xworld = xsh ? g_sh_world : 0; c.mw_xrank = xsh ? g_sh_rank : 0; c.mw_xcap = xcap; c.mw_mail = nullptr;
         if (xsh) g_xs.begin(g_sh_world, g_sh_rank, xcap);
         if (G <= 1 && !xsh) { c.mw = nullptr; c.mw_rank = 0; c.mw_world = 1; if (std::getenv("KAI_HOSTSIM_FRESH")) { HostBackend bf; Engine<HostBackend> ef(c, bf); ef.execute_victim_action(); ef.flush_index(); } else eng->execute_victim_action(); return KAI_OK; }
-        if (reps.empty() && G > 1) { reps.resize(G - 1); for (auto& r : reps) { if (int rc = alloc_ctx(r.pool, r.c)) return rc; if (r.pool.size() != pool.size()) return KAI_ERR_DEVICE_FAULT; } }
+        if (reps.empty() && G > 1) { reps.resize(G - 1); for (auto& r : reps) { if (int rc = build_ctx(r.pool, r.c, r.aux)) return rc; if (r.pool.size() != pool.size()) return KAI_ERR_DEVICE_FAULT; } }
         static MultiCtx M; std::memset(&M, 0, sizeof M); M.world = G; M.hit[0] = M.hit[1] = 0x7fffffff;
         c.mw = &M; c.mw_rank = 0; c.mw_world = G;
         for (int w = 1; w < G; w++) {

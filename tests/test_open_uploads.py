@@ -181,6 +181,86 @@ def test_a_handle_that_opens_session_after_session_fills_the_context_like_a_fres
         assert differing <= scratch, (k, differing, scratch)
 
 
+# ---- the library's open against the host simulation's: both fill the context through kai_ctx_build.hpp, each on its own arena
+SIM_AGAINST_LIB = r'''
+import ctypes as C, json, sys
+sys.path.insert(0, ROOT + "/tests"); sys.path.insert(0, ROOT)
+import kai_testlib as T
+lib = C.CDLL(LIB); sim = C.CDLL(SIM)
+lib.kai_last_error.restype = C.c_char_p; lib.kai_last_error.argtypes = [C.c_void_p]
+syn = T.pkg.synth
+def shapes():
+    yield "C1", syn.config(0)[:2]
+    yield "C2 at 20 %", syn.config(1, 0.2)[:2]
+    s, c, _ = syn.config(1, 0.5); syn.add_fractions(s, 7, frac=0.3); yield "C2 at 50 % with fractions", (s, c)
+    yield "C5-mixed at 3 %", syn.config(4, 0.03, mixed=True)[:2]
+    for ci, (snap, cfg, acts) in enumerate(T.broad_case(11)):
+        yield f"broad 11/{ci}", (snap, cfg)
+out = {}
+for name, (snap, cfg) in shapes():
+    h = C.c_void_p()
+    assert lib.kai_core_create(C.byref(cfg), 1, None, C.byref(h)) == 0
+    st = snap.as_struct()
+    rc = lib.kai_session_open(h, C.byref(st))
+    assert rc == 0, (name, rc, lib.kai_last_error(h))
+    sys.stderr.write("== " + name + chr(10)); sys.stderr.flush()
+    assert lib.kai_core_destroy(h) == 0
+    n = C.c_int64(0)
+    assert sim.kai_hostsim_open_digest(C.byref(cfg), C.byref(st), None, C.c_int64(0), C.byref(n)) == 0, name
+    buf = C.create_string_buffer(n.value + 1)
+    assert sim.kai_hostsim_open_digest(C.byref(cfg), C.byref(st), buf, C.c_int64(n.value), C.byref(n)) == 0, name
+    out[name] = buf.raw[:n.value].decode()
+print(json.dumps(out))
+'''
+
+
+def _digest_fields(text):
+    import re
+    return {int(m.group(1)): (int(m.group(2)), m.group(3)) for m in re.finditer(r"kai open digest: field (\d+) bytes (\d+) fnv (\w+)", text)}
+
+
+def unwritten_offsets(workdir):
+    """offsetof(KaiCtx, ...) of the arrays the open allocates without writing them: the operation log, the output staging, the GPU-group ids the open's first kernel resets"""
+    probe = os.path.join(str(workdir), "ctx_unwritten")
+    with open(probe + ".cpp", "w") as f:
+        f.write('#include <cmath>\n#include <math.h>\n#include <cstddef>\n#include <cstdio>\n#define KAI_SHARED_GPUS 1\n#include "%s"\nint main() { std::printf("%%zu %%zu %%zu\\n", offsetof(kai::KaiCtx, ops), offsetof(kai::KaiCtx, out_ops), offsetof(kai::KaiCtx, ng_id)); }\n'
+                % os.path.join(ROOT, "kai-scheduler_amd", "csrc", "kai_engine.hpp"))
+    subprocess.check_call(["g++", "-std=c++17", "-Wno-invalid-offsetof", "-o", probe, probe + ".cpp"])
+    return {int(x) for x in subprocess.check_output([probe], text=True).split()}
+
+
+def assert_sim_open_equals_library_open(lib, workdir, env, timeout=900):
+    """Opens each shape with the library `lib` (KAI_OPEN_DIGEST, a child process) and with the host simulation: every array of the session context holds the same bytes
+    before the first kernel, field for field — but for the arrays neither writes."""
+    from test_engine_hostsim import HostSim
+    HostSim.lib()  # (builds tests/host_sim/libhostsim.so when it is stale)
+    sim = os.environ.get("KAI_HOSTSIM_SO") or os.path.join(ROOT, "tests", "host_sim", "libhostsim.so")
+    e = dict(os.environ); e.pop("KAI_OPEN_FULL_UPLOADS", None); e["KAI_OPEN_DIGEST"] = "1"; e.update(env)
+    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\nLIB = {lib!r}\nSIM = {sim!r}\n" + SIM_AGAINST_LIB], env=e, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    of_sim = {k: _digest_fields(v) for k, v in json.loads(r.stdout.strip().splitlines()[-1]).items()}
+    of_lib, cur = {}, ""
+    for ln in r.stderr.splitlines():
+        if ln.startswith("== "): of_lib[ln[3:]] = _digest_fields(cur); cur = ""
+        else: cur += ln + "\n"
+    unwritten = unwritten_offsets(workdir)
+    assert len(unwritten) == 3
+    assert of_lib.keys() == of_sim.keys() and len(of_lib) >= 10
+    for k in of_lib:
+        assert of_lib[k].keys() == of_sim[k].keys(), k
+        differing = {f for f in of_lib[k] if of_lib[k][f] != of_sim[k][f]}
+        assert differing <= unwritten, (k, differing, unwritten)
+        assert len(of_lib[k]) - len(differing) > 100, k
+
+
+@pytest.mark.parametrize("env", [{}, {"KAI_OPEN_FULL_UPLOADS": "1"}], ids=["default", "full uploads"])
+def test_the_host_simulation_opens_the_session_the_library_opens(fake_lib, env):
+    """The CPU suite's sessions are SimSession's; the device's are kai_session_open's.  Both build the context with kai_ctx_build.hpp, and this holds the two arenas against each
+    other: the library's host side under the stand-in runtime (slab allocator, memsets, device-to-device copies, pinned staging) and the simulation's vectors end with the same
+    bytes in every array — an array one element short in the library, or a constant written on the device that differs from what is sent, shows here."""
+    assert_sim_open_equals_library_open(fake_lib, os.path.dirname(fake_lib), env)
+
+
 def test_the_shipped_library_under_the_stand_in_runtime(fake_lib):
     """The library as it ships (kai-scheduler_amd/csrc/libkai_core.so: hipcc -O3, device code embedded, linked against libamdhip64) with its HIP calls bound to the stand-in runtime
     by LD_PRELOAD: the open fills every array of the session context with the same bytes as the host-only build of this test, and what it leaves in device memory does not depend on

@@ -8,8 +8,9 @@
      the library's host clocks (KAI_PROF) split each update into staging + gather + checks, host bookkeeping and device work;
   4. the allocate that follows is hash-equal either way.
 
---open-ab LIB: also time kai_session_open of S with another build of the library (e.g. the parent commit's) in alternating child processes.
-Prints one JSON line; --out writes it to a file too.  Usage: python tools/update_timing.py [--scale 1.0] [--runs 7] [--open-ab LIB] [--out FILE]"""
+--open-ab LIB: also time kai_session_open of S with another build of the library (e.g. the parent commit's) in alternating child processes
+(--ab-procs of each, 2 by default; the medians of every process are reported beside the overall ones).
+Prints one JSON line; --out writes it to a file too.  Usage: python tools/update_timing.py [--scale 1.0] [--runs 7] [--open-ab LIB [--ab-procs 2]] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -106,6 +107,7 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--open-ab")
+    ap.add_argument("--ab-procs", type=int, default=2)  # child processes per library
     ap.add_argument("--out")
     a = ap.parse_args()
     os.environ["KAI_PROF"] = "1"
@@ -155,11 +157,12 @@ def main():
             res["deltas"].append(row)
     if a.open_ab:
         this_lib = os.path.join(ROOT, "kai-scheduler_amd", "csrc", "libkai_core.so")
-        ta, tb = [], []
-        for _ in range(2):  # alternating child processes: A B A B
-            ta += open_child(a.open_ab, a.scale, a.runs); tb += open_child(this_lib, a.scale, a.runs)
+        ta, tb, ma, mb = [], [], [], []
+        for _ in range(a.ab_procs):  # alternating child processes: A B A B ...
+            xa = open_child(a.open_ab, a.scale, a.runs); xb = open_child(this_lib, a.scale, a.runs)
+            ta += xa; tb += xb; ma.append(round(statistics.median(xa), 3)); mb.append(round(statistics.median(xb), 3))
         res["open_ab"] = {"other_lib_ms_median": statistics.median(ta), "this_lib_ms_median": statistics.median(tb), "other_lib_ms": [round(x, 3) for x in ta],
-                          "this_lib_ms": [round(x, 3) for x in tb]}
+                          "this_lib_ms": [round(x, 3) for x in tb], "other_lib_process_medians": ma, "this_lib_process_medians": mb}
     res["allocate_hash_equal"] = equal
     line = json.dumps(res)
     print(line)
