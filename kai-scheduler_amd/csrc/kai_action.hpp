@@ -312,7 +312,7 @@ int action_engine(kai_core* core, ActionRun& r) {
         // holds the whole session (only the fill's index is sharded), runs the same engine on it and commits the same operations; nothing is exchanged and nothing gets
         // faster, but a cycle that mixes both kinds of action (BASELINE config 4: allocate, consolidation, reclaim) runs on the group with the one-rank results.
         // The sharded fill left a class index of the own slice only: rebuild it over all nodes first.
-        if (c.use_index && c.NB) hipLaunchKernelGGL(k_index_build, dim3((c.NB + 3) / 4), dim3(256), 0, core->stream, c);
+        OpenLauncher ol{core}; index_drive(ol, c);
     }
     // dynamic LDS: upper levels of the class index, plus the job-order tree when it fits beside them (160 KiB per CU)
     size_t idx_b = lds_index_bytes(c.C, c.NSB), tree_b = lds_tree_bytes(c.Q);
@@ -400,10 +400,8 @@ int action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_cap,
     st = EngineState{}; st.total[0] = total[0]; st.total[1] = total[1]; st.total[2] = total[2];
     HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.st), &st, sizeof(st), hipMemcpyHostToDevice, core->stream));
     HIP_TRY(core, hipEventRecord(core->ev0, core->stream));
-    const int TB = 256;
-    if (core->index_stale) { if (c.use_index && c.NB) hipLaunchKernelGGL(k_index_build, dim3((c.NB + 3) / 4), dim3(TB), 0, core->stream, c); core->index_stale = false; }
-    if (c.J) hipLaunchKernelGGL(k_job_init, dim3((c.J + TB - 1) / TB), dim3(TB), 0, core->stream, c);
-    if (c.Q) hipLaunchKernelGGL(k_leaf_init, dim3((c.Q + 3) / 4), dim3(TB), 0, core->stream, c);
+    OpenLauncher ol{core};
+    action_init_drive(ol, c, core->index_stale);
     core->batch_plan_ms = core->batch_fill_ms = core->batch_apply_ms = 0;
     if (!victim) {  // the batch path (plan / fill / apply rounds, kai_batch.hpp) when the action qualifies
         DevLauncher dl{core};
@@ -421,7 +419,7 @@ int action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_cap,
     }
     const auto ta1 = std::chrono::steady_clock::now();
     if (!r.bs.ran) KAI_TRY(action_engine(core, r));
-    if (c.J && !victim) hipLaunchKernelGGL(k_drain, dim3(std::min(2048, (c.J + 255) / 256)), dim3(256), 0, core->stream, c, core->aux.slot_queue);
+    if (!victim) drain_drive(ol, c, core->aux);
     HIP_TRY(core, hipGetLastError());
     HIP_TRY(core, hipEventRecord(core->ev1, core->stream));
     HIP_TRY(core, hipMemcpyAsync(&st, KAI_VP(c.st), sizeof(st), hipMemcpyDeviceToHost, core->stream));

@@ -2601,7 +2601,7 @@ struct Engine {
         }
         return ok ? 1 : 0;
     }
-    // What the allocate loop does with a job once no class has a fitting node (used by k_drain and the host twin): the job is
+    // What the allocate loop does with a job once no class has a fitting node (used by k_drain: drain_body of kai_open_kernels.hpp): the job is
     // attempted, passes or fails the queue-capacity gate, and its first task finds no node.  Touches only job j's own cache.
     KAI_HD void drain_job(int j, int64_t& attempted, int64_t& decisions, int64_t& rollbacks) {
         attempted++;
@@ -2793,7 +2793,7 @@ KAI_HD void divide_sibling_set(const KaiCtx& c, const int32_t* kids, int nk, int
 }
 
 // ======================================================================================================
-// action init, per job and per leaf queue (run by k_job_init / k_leaf_init on the whole chip; host_sim runs them serially)
+// action init, per job and per leaf queue (run by k_job_init / k_leaf_init on the whole chip: kai_open_kernels.hpp, whose bodies host_sim runs on the emulator)
 // ======================================================================================================
 // InitializeWithJobs filters for the allocate action (actions/utils/input_jobs.go:24-63) + the job's elastic state:
 // 0/1/2 = eligible with minAvailableState below/exactly/above, 3 = filtered out
@@ -2813,7 +2813,7 @@ KAI_HD uint8_t job_init_state(const KaiCtx& c, int j) {
     return below ? 0 : exactly ? 1 : 2;
 }
 
-// job-order tree node of queue q at action start (k_leaf_init lane 0 / host_sim): static fields + queued jobs of a leaf
+// job-order tree node of queue q at action start (k_qnode_static, k_leaf_init lane 0): static fields + queued jobs of a leaf
 KAI_HD void qnode_init(const KaiCtx& c, int q, int queued) {
     QNode n; n.dom_with_job = 0; n.dom_no_job = 0; n.best_job = -1; n.prio = c.q_prio[q]; n.heap_off = c.q_child_off[q]; n.parent = c.q_parent[q];
     bool leaf = c.q_child_off[q + 1] == c.q_child_off[q];

@@ -1,19 +1,18 @@
 // kai_kernels.hpp — gfx950 kernels of the scheduling-cycle core (included by kai_core.hip only).
 //
-//  * session-open kernels: node accounting from the pods, proportion totals, queue usage roll-up
-//    (segmented reductions pods → job → leaf queue → ancestors), fair-share division per tree level,
-//    and the class-index build (one wavefront per 64-node block, every scan class);
-//  * action-init kernels: per-job eligibility / elastic state, per-leaf-queue stable compaction into job order;
 //  * the persistent action kernel: wave 0 / lane 0 drives kai::Engine, the other 15 wavefronts of the workgroup
 //    keep the class index current (block refresh) and serve brute-force node scans out of the HBM-resident
 //    node SoA (resource-major, so a wavefront reads 64 consecutive nodes of one resource = one 512-byte request);
-//  * the drain kernel: once no class has a fitting node, the jobs still queued are resolved chip-wide.
+//  * kai_best_node's kernel on the same service loop.
+//
+// The session-open, action-init and drain kernels are kai_open_kernels.hpp's: bodies on kai_simt.hpp, which the host simulation runs too.
 //
 // wave = 64 lanes; workgroup = 512 threads = 8 wavefronts (1 control + 7 service waves).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "kai_engine.hpp"
+#include "kai_open_kernels.hpp"
 #include "kai_wave.hpp"
 
 namespace kai {
@@ -23,294 +22,9 @@ constexpr int WAVES = WG / 64;  // 8
 constexpr int SCAN_LANES = WG - 64;
 constexpr int SVC = WAVES - 1;  // service waves
 
-// ------------------------------------------------------------------------------------------------------
-// session open
-// ------------------------------------------------------------------------------------------------------
-
-// NodeInfo.AddTask for every active-used pod of the snapshot (api/node_info/node_info.go:384-493).
-// Quantities are integers in float64 (milli-cores, bytes, devices, pod counts) so the f64 atomics commute exactly.
-__global__ void k_node_accounting(KaiCtx c) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= c.P) return;
-    int s = c.p_status[p], n = c.p_node[p];
-    c.p_on_node[p] = -1; c.p_on_node_status[p] = 0; c.p_accepted[p] = 0; c.p_virtual[p] = 0;
-    if (!st_active_used(s) || n < 0 || n >= c.N) return;
-    c.p_on_node[p] = n; c.p_on_node_status[p] = s; c.p_accepted[p] = 1;
-    for (int r = 0; r < c.R; r++) {
-        double v = c.p_req[(size_t)r * c.P + p]; if (v == 0) continue;
-        size_t i = (size_t)r * c.N + n;
-        atomicAdd(&c.n_used[i], v);
-        if (s == KAI_POD_RELEASING) { atomicAdd(&c.n_rel[i], v); atomicAdd(&c.n_idle[i], -v); }
-        else if (s == KAI_POD_PIPELINED) atomicAdd(&c.n_rel[i], -v);
-        else atomicAdd(&c.n_idle[i], -v);
-    }
-}
-
-#ifdef KAI_SHARED_GPUS
-// shared GPUs: NodeInfo.AddTask of a node's active pods in UID order by ONE lane per node — addSharedTaskResources' guards read what the
-// pods before them left behind (api/node_info/gpu_sharing_node_info.go:83-136), so the order inside a node is part of the result
-__global__ void k_pod_accounting_reset(KaiCtx c) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= c.P) return;
-    c.p_on_node[p] = -1; c.p_on_node_status[p] = 0; c.p_accepted[p] = 0; c.p_virtual[p] = 0; c.p_on_group[p] = -1;
-}
-__global__ void k_node_accounting_shared(KaiCtx c, const int32_t* np_off, const int32_t* np_pods) {
-    int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= c.N) return;
-    for (int i = np_off[n]; i < np_off[n + 1]; i++) {
-        const int p = np_pods[i], st = c.p_status[p];
-        c.p_on_node[p] = n; c.p_on_node_status[p] = st; c.p_accepted[p] = 1;
-        const bool frac = c.p_shared[p] != 0;
-        if (frac && c.p_group[p] >= 0) c.p_on_group[p] = c.p_group[p];
-        for (int r = 0; r < c.R; r++) {
-            if (r == KAI_RES_GPU && frac) continue;  // getAcceptedTaskResourceWithoutSharedGPU :52-66
-            const double v = c.p_req[(size_t)r * c.P + p]; if (v == 0) continue;
-            const size_t x = (size_t)r * c.N + n;
-            c.n_used[x] += v;
-            if (st == KAI_POD_RELEASING) { c.n_rel[x] += v; c.n_idle[x] -= v; } else if (st == KAI_POD_PIPELINED) c.n_rel[x] -= v; else c.n_idle[x] -= v;
-        }
-        if (frac && c.p_on_group[p] >= 0) { SgNode g{c, n}; if (!g.add(st, c.p_mem[p], c.p_on_group[p])) { c.st->fault = FAULT_INTERNAL; c.st->fault_line = __LINE__; } }
-    }
-    { SgNode g{c, n}; g.refit(); }  // the class keys' summary bits of the node's groups (also clears what an earlier session of this snapshot left: kai_session_reset)
-}
-#endif
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// proportion.setTotalResources (plugins/proportion/proportion.go:252-288): Σ allocatable of ready nodes …
-__global__ void k_total_nodes(KaiCtx c) {
-    double acc[3] = {0, 0, 0};
-    for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < c.N; n += gridDim.x * blockDim.x) {
-        uint32_t f = c.n_flags[n];
-        if (f & KAI_NODE_NOT_READY) continue;
-        bool ignore_gpus = c.restrict_nodes && !(f & KAI_NODE_GPU_WORKER);
-        acc[KAI_Q_CPU] += c.n_alloc[(size_t)KAI_RES_CPU * c.N + n];
-        acc[KAI_Q_MEM] += c.n_alloc[(size_t)KAI_RES_MEM * c.N + n];
-        if (!ignore_gpus) {  // QuantifyResource(Allocatable): GPUs + MIG instances by weight (resource_info.go:177-194)
-            acc[KAI_Q_GPU] += c.n_alloc[(size_t)KAI_RES_GPU * c.N + n];
-#ifdef KAI_SHARED_GPUS
-            if (c.mig_on) for (int r = KAI_RES_PODS + 1; r < c.R; r++) if (c.res_mig_g[r] > 0) acc[KAI_Q_GPU] += (double)c.res_mig_g[r] * c.n_alloc[(size_t)r * c.N + n];
-#endif
-        }
-    }
-    for (int k = 0; k < 3; k++) { double v = wave_sum(acc[k]); if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(&c.st->total[k], v); }
-}
-// … minus the active pods of other schedulers on those nodes (:276-285)
-__global__ void k_total_foreign(KaiCtx c) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= c.P) return;
-    if (!(c.p_flags[p] & KAI_POD_FOREIGN_SCHEDULER)) return;
-    int n = c.p_on_node[p]; if (n < 0) return;
-    if (!st_active_used(c.p_on_node_status[p])) return;
-    if (c.n_flags[n] & KAI_NODE_NOT_READY) return;
-    atomicAdd(&c.st->total[KAI_Q_CPU], -c.p_req[(size_t)KAI_RES_CPU * c.P + p]);
-    atomicAdd(&c.st->total[KAI_Q_MEM], -c.p_req[(size_t)KAI_RES_MEM * c.P + p]);
-#ifdef KAI_SHARED_GPUS
-    atomicAdd(&c.st->total[KAI_Q_GPU], -(c.quota_on ? c.p_quota_gpu[p] : c.p_req[(size_t)KAI_RES_GPU * c.P + p]));  // QuantifyResourceRequirements(ResReq)
-#else
-    atomicAdd(&c.st->total[KAI_Q_GPU], -c.p_req[(size_t)KAI_RES_GPU * c.P + p]);
-#endif
-}
-
-// per-job sums + pod-set / job counters (api/podgroup_info/job_info.go:208-226, subgroup_info/podset.go:56-77).
-// jsum[9][J]: (allocated, allocated_np, request) × (CPU, Memory, GPU) — proportion.updateQueuesCurrentResourceUsage :347-401
-__global__ void k_job_usage(KaiCtx c, double* jsum) {
-    int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= c.J) return;
-    double al[3] = {0, 0, 0}, rq[3] = {0, 0, 0}, ja[3] = {0, 0, 0};
-    int pending = 0;
-    for (int k = 0; k < c.j_n_ps[j]; k++) { int s = c.j_first_ps[j] + k; c.s_active_alloc[s] = 0; c.s_active_used[s] = 0; c.s_alive[s] = 0; c.s_gated[s] = 0; c.s_pipelined[s] = 0; }
-    for (int i = 0; i < c.j_n_pods[j]; i++) {
-        int p = c.j_first_pod[j] + i, s = c.p_status[p], ps = c.p_podset[p];
-        if (st_active_allocated(s)) c.s_active_alloc[ps]++;
-        if (st_active_used(s)) c.s_active_used[ps]++;
-        if (st_alive(s)) c.s_alive[ps]++;
-        if (s == KAI_POD_GATED) c.s_gated[ps]++;
-        if (s == KAI_POD_PIPELINED) c.s_pipelined[ps]++;
-        if (s == KAI_POD_PENDING) pending++;
-        double q[3] = {c.p_req[(size_t)KAI_RES_CPU * c.P + p], c.p_req[(size_t)KAI_RES_MEM * c.P + p], c.p_req[(size_t)KAI_RES_GPU * c.P + p]};
-        double qa = q[2], qp = q[2], qq = q[2];  // GPU quota of AcceptedResource / GPU weight of a pending request / quota of ResReq: they differ from ResReq.GPUs() for gpu-memory and MIG requests
-#ifdef KAI_SHARED_GPUS
-        if (c.quota_on) { qa = c.p_acc_gpu[p]; qp = c.p_pend_gpu[p]; qq = c.p_quota_gpu[p]; }
-#endif
-        if (st_allocated(s)) {
-            for (int k = 0; k < 3; k++) ja[k] += k == 2 ? qq : q[k];  // PodGroupInfo.Allocated carries the MIG instances (job_info.go:231-251): QuantifyResource of it
-            if (c.p_accepted[p]) for (int k = 0; k < 3; k++) { const double v = k == 2 ? qa : q[k]; al[k] += v; rq[k] += v; }  // AcceptedResource is empty for a pod no node holds
-        } else if (s == KAI_POD_PENDING) {
-            for (int k = 0; k < 3; k++) rq[k] += k == 2 ? qp : q[k];
-        }
-    }
-    c.j_n_pending[j] = pending; c.j_tta_valid[j] = 0; c.j_tta_n[j] = 0;
-    bool np = !c.j_preempt[j];
-    for (int k = 0; k < 3; k++) {
-        c.j_allocated[(size_t)j * 4 + k] = ja[k];
-        jsum[(size_t)(0 + k) * c.J + j] = al[k]; jsum[(size_t)(3 + k) * c.J + j] = np ? al[k] : 0.0; jsum[(size_t)(6 + k) * c.J + j] = rq[k];
-    }
-}
-// one wavefront per leaf queue: segmented reduction over the queue's jobs (jobs_static is CSR by q_job_off; the sum order is
-// fixed by the lane stride, and the addends are integer-valued, so the result does not depend on it)
-__global__ void k_leaf_usage(KaiCtx c, const double* jsum) {
-    int q = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (q >= c.Q) return;
-    int lane = threadIdx.x & 63, b = c.q_job_off[q], e = c.q_job_off[q + 1];
-    double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = b + lane; i < e; i += 64) { int j = c.jobs_static[i]; for (int x = 0; x < 9; x++) acc[x] += jsum[(size_t)x * c.J + j]; }
-    for (int x = 0; x < 9; x++) acc[x] = wave_sum(acc[x]);
-    if (lane == 0) for (int k = 0; k < 3; k++) {
-        QShare& s = c.q_share[(size_t)q * 3 + k];
-        s.allocated = acc[k]; s.allocated_np = acc[3 + k]; s.request = acc[6 + k]; s.fair = 0;
-    }
-}
-// ancestors: level by level up the tree (leaf = height 0), one lane per (inner queue, field): a segmented reduction over the queue's children,
-// added in child-index order like the sequential roll-up.  One workgroup; h_nodes / h_off list the queues by height (HostPrep::build_batch).
-__global__ void k_tree_usage(KaiCtx c, const int32_t* h_off, const int32_t* h_nodes, int n_h) {
-    for (int h = 1; h < n_h - 1; h++) {  // the virtual root (last height) holds no shares
-        const int b = h_off[h], e = h_off[h + 1];
-        for (int t = threadIdx.x; t < (e - b) * 9; t += blockDim.x) {
-            const int x = h_nodes[b + t / 9], f = (t % 9) / 3, k = t % 3;
-            if (x >= c.Q) continue;
-            double acc = 0.0;
-            for (int i = c.q_child_off[x]; i < c.q_child_off[x + 1]; i++) {
-                const QShare& s = c.q_share[(size_t)c.q_children[i] * 3 + k];
-                acc += f == 0 ? s.allocated : f == 1 ? s.allocated_np : s.request;
-            }
-            QShare& d = c.q_share[(size_t)x * 3 + k];
-            if (f == 0) d.allocated += acc; else if (f == 1) d.allocated_np += acc; else d.request += acc;
-        }
-        __threadfence(); __syncthreads();
-    }
-}
-// proportion.setFairShareForQueues (plugins/proportion/proportion.go:410-423), one tree level per launch (a level's totals are the parents' fair
-// shares of the level above).  One wavefront per (sibling set, resource): the lanes stage the set — shares, priorities, creation times — into LDS,
-// lane 0 runs the division (resource_division.go:26-357: rounds whose outcome feeds the next, sequential by construction) on the staged copy, the
-// lanes write the fair shares back.  Sets of more than 64 queues run on the session arrays directly.
-struct SiblingsLds {
-    QShare* sh; int64_t* pr; int64_t* cr; uint32_t* ui; double* w; double* ra; uint8_t* rh;
-    __device__ QShare& share(int i) const { return sh[i]; }
-    __device__ int64_t prio(int i) const { return pr[i]; }
-    __device__ int64_t created(int i) const { return cr[i]; }
-    __device__ uint32_t uid(int i) const { return ui[i]; }
-    __device__ double& weight(int i) const { return w[i]; }
-    __device__ double& rem_amt(int i) const { return ra[i]; }
-    __device__ uint8_t& rem_has(int i) const { return rh[i]; }
-};
-constexpr int FS_WAVES = 4, FS_MAX = 64;
-__global__ void __launch_bounds__(FS_WAVES * 64) k_fair_share_level(KaiCtx c, const int32_t* lvl_parents, int first, int count, double* weight, double* rem_amt, uint8_t* rem_has) {
-    __shared__ QShare s_sh[FS_WAVES][FS_MAX]; __shared__ int64_t s_pr[FS_WAVES][FS_MAX], s_cr[FS_WAVES][FS_MAX];
-    __shared__ uint32_t s_ui[FS_WAVES][FS_MAX]; __shared__ double s_w[FS_WAVES][FS_MAX], s_ra[FS_WAVES][FS_MAX]; __shared__ uint8_t s_rh[FS_WAVES][FS_MAX];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, t = blockIdx.x * FS_WAVES + wave;
-    if (t >= count * 3) return;
-    const int par = lvl_parents[first + t / 3], k = t % 3;
-    const double total = par == c.Q ? c.st->total[k] : c.q_share[(size_t)par * 3 + k].fair;
-    const int32_t* kids = c.q_children + c.q_child_off[par];
-    const int nk = c.q_child_off[par + 1] - c.q_child_off[par];
-    if (nk > FS_MAX) { if (lane == 0) divide_sibling_set(c, kids, nk, k, total, c.k_value, weight + (size_t)k * c.Q, rem_amt + (size_t)k * c.Q, rem_has + (size_t)k * c.Q); return; }
-    if (lane < nk) { const int q = kids[lane]; s_sh[wave][lane] = c.q_share[(size_t)q * 3 + k]; s_pr[wave][lane] = c.q_prio[q]; s_cr[wave][lane] = c.q_created[q]; s_ui[wave][lane] = c.q_uid_rank[q]; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    if (lane == 0) { SiblingsLds v{s_sh[wave], s_pr[wave], s_cr[wave], s_ui[wave], s_w[wave], s_ra[wave], s_rh[wave]}; divide_sibling_view(v, nk, total, c.k_value); }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    if (lane < nk) c.q_share[(size_t)kids[lane] * 3 + k].fair = s_sh[wave][lane].fair;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// class index
-// ------------------------------------------------------------------------------------------------------
 // arg-max of (key, node) over a wavefront; lanes are in ascending node / block order, ties go to the lowest lane (kai_wave.hpp)
 __device__ __forceinline__ void wave_argmax(uint64_t& k, int& n) {
     unsigned long long kk = k; wave_argmax_first(kk, n); k = kk;
-}
-// L1 of the class index: one wavefront per 64-node block, every class (node state is read once per class from L1/L2)
-__global__ void k_index_build(KaiCtx c) {
-    int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (b >= c.NB) return;
-    int lane = threadIdx.x & 63, n = b * KAI_BLOCK + lane;
-    NodeRegs ns; load_node(c, n < c.N ? n : 0, ns);
-    for (int k = 0; k < c.C; k++) {
-        uint64_t key = n < c.N ? class_key_regs(c, c.cls[k], ns) : 0; int bn = n;
-        wave_argmax(key, bn);
-        if (lane == 0) { c.sum1_key[(size_t)k * c.NB + b] = key; c.sum1_node[(size_t)k * c.NB + b] = bn; }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// action init
-// ------------------------------------------------------------------------------------------------------
-struct NullBackend {  // kernels that only need the engine's pure helpers
-    static constexpr bool kVictim = false;
-    template <class T> __device__ static void assume_tree(T*) {}
-    const KaiCtx* cref = nullptr; EngineLocal loc;
-    static constexpr bool kBig = false;  // (no scan lane ever reads the control lane's larger data; big() only has to exist)
-    __device__ static EngineBig& big();
-    __device__ void bind(const KaiCtx& c) { cref = &c; }
-    __device__ const KaiCtx& ctx() const { return *cref; }
-    __device__ EngineLocal& local() { return loc; }
-    __device__ void minmax(const KaiCtx&, int, double&, double&) {}
-    __device__ bool topo_scan(const KaiCtx&, TopoScan&) { return false; }
-    __device__ bool pfor(const KaiCtx&, const PforReq&) { return false; }
-    __device__ void or32(uint32_t* w, uint32_t bits) { atomicOr(w, bits); }
-    __device__ static void add_f64(double* p, double v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }  // the roll-ups of subSetNodesFn: one workgroup, one L2
-    __device__ static void add_i32(int32_t* p, int32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-    __device__ static double coh_f64(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }  // coherent with the atomics of workgroups on other XCDs
-    __device__ static int32_t coh_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ int best_node(const KaiCtx&, const ScanReq&, double* = nullptr) { return -1; }
-    __device__ bool eval_nodes(const KaiCtx&, const ScanReq&, const int32_t*, int, double*, uint8_t*) { return false; }
-    __device__ void begin(const KaiCtx&) {}
-    __device__ bool dirty_add(int) { return true; }
-    __device__ int dirty_count() { return 0; }
-    __device__ void refresh(const KaiCtx&) {}
-    __device__ void class_top(const KaiCtx&, int, uint64_t& k, int& n) { k = 0; n = -1; }
-    __device__ bool all_dead(const KaiCtx&) { return false; }
-    __device__ void stage_async(const KaiCtx&, int) {}
-    __device__ bool staged(int) { return false; }
-    __device__ void hot(const KaiCtx&, QNode*&, int32_t*&, int32_t*&) {}
-    __device__ bool sim_tree(QNode*&, int32_t*&, int32_t*&) { return false; }
-    __device__ int64_t clock() { return 0; }
-};
-
-// static fields of the job-order tree records (parent chain, priority, heap offsets): valid from session open on
-__global__ void k_qnode_static(KaiCtx c) {
-    int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < c.Q) qnode_init(c, q, 0);
-}
-__global__ void k_job_init(KaiCtx c) {
-    int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= c.J) return;
-    uint8_t st = job_init_state(c, j);
-    c.j_state[j] = st;
-    // the tasks-to-allocate chunk of every queued job (allocation_info.go:27-113), which the queue comparator reads for the best
-    // job of each queue: computed here chip-wide instead of lazily by the control lane.  Nothing is virtual before the first
-    // statement of an action, so the chunk does not depend on isRealAllocation.
-    if (st != 3 && c.j_n_ps[j] <= 64) { NullBackend nb; Engine<NullBackend> eng(c, nb); eng.ensure_tta(j, true); }
-}
-// One wavefront per leaf queue: stable compaction of the eligible "below minAvailable" jobs (host order: priority desc,
-// creation, uid) into the leaf's sorted region; the few jobs in another elastic state go to the leaf's side heap.
-__global__ void k_leaf_init(KaiCtx c) {
-    int q = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (q >= c.Q) return;
-    int lane = threadIdx.x & 63, b = c.q_job_off[q], e = c.q_job_off[q + 1];
-    int cnt = 0, side = 0;
-    const unsigned long long lt = (1ull << lane) - 1;
-    for (int base = b; base < e; base += 64) {
-        int i = base + lane, j = i < e ? c.jobs_static[i] : -1;
-        int st = j >= 0 ? c.j_state[j] : 3;
-        unsigned long long m0 = __ballot(st == 0), m12 = __ballot(st == 1 || st == 2);
-        if (st == 0) c.lq_sorted[b + cnt + __popcll(m0 & lt)] = j;
-        if (st == 1 || st == 2) c.lq_side[b + side + __popcll(m12 & lt)] = j;
-        cnt += __popcll(m0); side += __popcll(m12);
-    }
-    __threadfence_block();
-    if (lane == 0) {
-        c.lq_cur[q] = 0; c.lq_end[q] = cnt; c.lq_side_len[q] = 0;
-        qnode_init(c, q, cnt + side);
-        if (side) {
-            NullBackend nb; Engine<NullBackend> eng(c, nb);
-            int32_t* h = c.lq_side + b;
-            for (int i = 0; i < side; i++) { c.lq_side_len[q] = i + 1; eng.heap_up(h, i, typename Engine<NullBackend>::JobLess{&eng}); }
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -979,27 +693,6 @@ __global__ void __launch_bounds__(WG) k_action(const KaiCtx* __restrict__ cp, in
     if constexpr (!VICTIM) { c.st->prof[36] = sh.t_seg[0]; c.st->prof[37] = sh.t_seg[1]; c.st->prof[38] = sh.t_seg[2]; c.st->prof[39] = sh.t_seg[3]; }  // scan grid: publish (release fence), own slice, wait for the fold, commands
 #endif
     be.finish();
-}
-
-// Once no class has a fitting node at a committed state, every job still queued is attempted, gated and fails at its first
-// task without changing any state (Engine::drain_job): resolve them chip-wide.  Slot i of a leaf's region holds a job of the
-// sorted part if cur <= pos < end and a job of the side heap if pos < side_len.
-__global__ void k_drain(KaiCtx c, const int32_t* slot_queue) {
-    if (!c.st->drain_pending) return;
-    NullBackend nb; Engine<NullBackend> eng(c, nb);
-    int64_t att = 0, dec = 0, rb = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < c.J; i += gridDim.x * blockDim.x) {
-        int q = slot_queue[i]; if (q < 0) continue;
-        int pos = i - c.q_job_off[q];
-        if (pos >= c.lq_cur[q] && pos < c.lq_end[q]) eng.drain_job(c.lq_sorted[i], att, dec, rb);
-        if (pos < c.lq_side_len[q]) eng.drain_job(c.lq_side[i], att, dec, rb);
-    }
-    for (int o = 32; o > 0; o >>= 1) { att += __shfl_xor((long long)att, o, 64); dec += __shfl_xor((long long)dec, o, 64); rb += __shfl_xor((long long)rb, o, 64); }
-    if ((threadIdx.x & 63) == 0 && att) {
-        atomicAdd((unsigned long long*)&c.st->jobs_attempted, (unsigned long long)att); atomicAdd((unsigned long long*)&c.st->decisions, (unsigned long long)dec);
-        atomicAdd((unsigned long long*)&c.st->rollbacks, (unsigned long long)rb);
-        atomicAdd((unsigned long long*)&c.st->drained_jobs, (unsigned long long)att); atomicAdd((unsigned long long*)&c.st->drained_decisions, (unsigned long long)dec);
-    }
 }
 
 // kai_best_node: one OrderedNodesByTask + FittingNode against the current session state (brute-force scan)

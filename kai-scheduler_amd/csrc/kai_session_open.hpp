@@ -1,34 +1,43 @@
-// kai_session_open.hpp — kai_session_open's host side around the context builder (kai_ctx_build.hpp), the kernels behind the open and the reset (launch_open_kernels), kai_session_reset's body (reset_state).
+// kai_session_open.hpp — kai_session_open's host side around the context builder (kai_ctx_build.hpp), the launcher of kai_open_kernels.hpp's sequences (OpenLauncher), the kernels behind the open and the reset (open_kernels), kai_session_reset's body (reset_state).
 #pragma once
 #include "kai_handle.hpp"
 namespace {
+// the session-open, action-init and drain kernels on the session's stream (the Launcher of kai_open_kernels.hpp's sequences)
+struct OpenLauncher {
+    kai_core* core; hipError_t err = hipSuccess;
+    template <class P> void fill32(P p, int byte, size_t n) { const hipError_t e = hipMemsetAsync(KAI_VP(p), byte, n * 4, core->stream); if (err == hipSuccess) err = e; }
+    void node_accounting(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_node_accounting, dim3(g), dim3(b), 0, core->stream, c); }
+    void pod_accounting_reset(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_pod_accounting_reset, dim3(g), dim3(b), 0, core->stream, c); }
+    void node_accounting_shared(int g, int b, const KaiCtx& c, const int32_t* np_off, const int32_t* np_pods) { hipLaunchKernelGGL(k_node_accounting_shared, dim3(g), dim3(b), 0, core->stream, c, np_off, np_pods); }
+    void total_nodes(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_total_nodes, dim3(g), dim3(b), 0, core->stream, c); }
+    void total_foreign(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_total_foreign, dim3(g), dim3(b), 0, core->stream, c); }
+    void job_usage(int g, int b, const KaiCtx& c, double* jsum) { hipLaunchKernelGGL(k_job_usage, dim3(g), dim3(b), 0, core->stream, c, jsum); }
+    void leaf_usage(int g, int b, const KaiCtx& c, const double* jsum) { hipLaunchKernelGGL(k_leaf_usage, dim3(g), dim3(b), 0, core->stream, c, jsum); }
+    void tree_usage(int g, int b, const KaiCtx& c, const int32_t* h_off, const int32_t* h_nodes, int n_h) { hipLaunchKernelGGL(k_tree_usage, dim3(g), dim3(b), 0, core->stream, c, h_off, h_nodes, n_h); }
+    void fair_share_level(int g, int b, const KaiCtx& c, const int32_t* lvl_parents, int first, int count, double* weight, double* rem_amt, uint8_t* rem_has) { hipLaunchKernelGGL(k_fair_share_level, dim3(g), dim3(b), 0, core->stream, c, lvl_parents, first, count, weight, rem_amt, rem_has); }
+    void qnode_static(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_qnode_static, dim3(g), dim3(b), 0, core->stream, c); }
+    void index_build(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_index_build, dim3(g), dim3(b), 0, core->stream, c); }
+    void job_init(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_job_init, dim3(g), dim3(b), 0, core->stream, c); }
+    void leaf_init(int g, int b, const KaiCtx& c) { hipLaunchKernelGGL(k_leaf_init, dim3(g), dim3(b), 0, core->stream, c); }
+    void drain(int g, int b, const KaiCtx& c, const int32_t* slot_queue) { hipLaunchKernelGGL(k_drain, dim3(g), dim3(b), 0, core->stream, c, slot_queue); }
+};
+// FNV-1a of every array of the session context, a line per KaiCtx field under `prefix` (KAI_OPEN_DIGEST; tests/test_open_uploads.py, tests/test_gpu_open_digest.py)
+int open_digest(kai_core* core, const char* prefix) {
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    for (const kai_core::AllocRec& a : core->allocs) {
+        std::vector<unsigned char> h(a.bytes);
+        HIP_TRY(core, hipMemcpyAsync(h.data(), a.base, a.bytes, hipMemcpyDeviceToHost, core->stream)); HIP_TRY(core, hipStreamSynchronize(core->stream));
+        uint64_t f = 1469598103934665603ull; for (unsigned char x : h) { f ^= x; f *= 1099511628211ull; }
+        std::fprintf(stderr, "%s: field %zu bytes %zu fnv %016llx\n", prefix, a.field_off, a.bytes, (unsigned long long)f);
+    }
+    return KAI_OK;
+}
 // session-open kernels over the HBM-resident snapshot (used by kai_session_open and kai_session_reset)
-int launch_open_kernels(kai_core* core) {
-    KaiCtx& c = core->ctx;
-    const int N = c.N, P = c.P, J = c.J, Q = c.Q;
-    const int TB = 256;
-    if (core->shared) {  // shared GPUs: group tables reset, then every node adds its pods in UID order (one lane per node)
-        HIP_TRY(core, hipMemsetAsync(KAI_VP(c.ng_id), 0xFF, sizeof(int32_t) * (size_t)std::max(N, 1) * KAI_GMAX, core->stream));
-        if (P) hipLaunchKernelGGL(k_pod_accounting_reset, dim3((P + TB - 1) / TB), dim3(TB), 0, core->stream, c);
-        if (N) hipLaunchKernelGGL(k_node_accounting_shared, dim3((N + TB - 1) / TB), dim3(TB), 0, core->stream, c, (const int32_t*)core->aux.np_off, (const int32_t*)core->aux.np_pods);
-    } else if (P) hipLaunchKernelGGL(k_node_accounting, dim3((P + TB - 1) / TB), dim3(TB), 0, core->stream, c);
-    if (core->cfg.plugins & KAI_PLUGIN_PROPORTION) {
-        if (N) hipLaunchKernelGGL(k_total_nodes, dim3(std::min(1024, (N + TB - 1) / TB)), dim3(TB), 0, core->stream, c);
-        if (P) hipLaunchKernelGGL(k_total_foreign, dim3((P + TB - 1) / TB), dim3(TB), 0, core->stream, c);
-    }
-    if (J) hipLaunchKernelGGL(k_job_usage, dim3((J + TB - 1) / TB), dim3(TB), 0, core->stream, c, core->aux.jsum);
-    if (core->cfg.plugins & KAI_PLUGIN_PROPORTION) {
-        if (Q) hipLaunchKernelGGL(k_leaf_usage, dim3((Q + 3) / 4), dim3(TB), 0, core->stream, c, core->aux.jsum);
-        if (Q) hipLaunchKernelGGL(k_tree_usage, dim3(1), dim3(1024), 0, core->stream, c, (const int32_t*)core->aux.h_off, (const int32_t*)core->aux.h_nodes, core->n_heights);
-        for (int l = 0; Q && l < core->n_levels; l++) {  // a level's totals are the fair shares of the level above: one launch per level
-            const int first = core->h_lvl_off[l], count = core->h_lvl_off[l + 1] - first;
-            if (count > 0) hipLaunchKernelGGL(k_fair_share_level, dim3((count * 3 + FS_WAVES - 1) / FS_WAVES), dim3(FS_WAVES * 64), 0, core->stream, c, (const int32_t*)core->aux.lvl_parents, first, count,
-                                              core->aux.weight, core->aux.rem_amt, core->aux.rem_has);
-        }
-    }
-    if (Q) hipLaunchKernelGGL(k_qnode_static, dim3((Q + TB - 1) / TB), dim3(TB), 0, core->stream, c);
-    if (c.use_index && c.NB) hipLaunchKernelGGL(k_index_build, dim3((c.NB + 3) / 4), dim3(TB), 0, core->stream, c);
-    HIP_TRY(core, hipGetLastError());
+int open_kernels(kai_core* core) {
+    OpenLauncher l{core};
+    open_drive(l, core->ctx, core->aux, OpenShape{core->n_levels, core->h_lvl_off.data(), core->n_heights, core->cfg.plugins, core->shared});
+    HIP_TRY(core, l.err); HIP_TRY(core, hipGetLastError());
+    core->index_stale = false;
     return KAI_OK;
 }
 // ---- kai_session_open: session_open_impl below is the checks, the context builder's calls (kai_ctx_build.hpp), the handle's bookkeeping, the baselines and the kernels
@@ -143,19 +152,13 @@ int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     KAI_TRY(ctx_build(arena, c, core->aux, CtxBuildIn{core->cfg, s, prep, sp, std::getenv("KAI_OPEN_FULL_UPLOADS") != nullptr, 1}, built));
     open_bookkeeping(core, s, built);
     KAI_TRY(open_baselines(core));
-    if (std::getenv("KAI_OPEN_DIGEST")) {  // diagnostic: what the open put into every array of the session context, before its first kernel (FNV-1a per KaiCtx field; tests/test_open_uploads.py)
-        HIP_TRY(core, hipStreamSynchronize(core->stream));
-        for (const kai_core::AllocRec& a : core->allocs) {
-            std::vector<unsigned char> h(a.bytes);
-            HIP_TRY(core, hipMemcpyAsync(h.data(), a.base, a.bytes, hipMemcpyDeviceToHost, core->stream)); HIP_TRY(core, hipStreamSynchronize(core->stream));
-            uint64_t f = 1469598103934665603ull; for (unsigned char x : h) { f ^= x; f *= 1099511628211ull; }
-            std::fprintf(stderr, "kai open digest: field %zu bytes %zu fnv %016llx\n", a.field_off, a.bytes, (unsigned long long)f);
-        }
-    }
-    KAI_TRY(launch_open_kernels(core)); core->index_stale = false;
+    const bool digest = std::getenv("KAI_OPEN_DIGEST") != nullptr;  // diagnostic: what the open put into every array of the session context before its first kernel, and what its kernels left
+    if (digest) KAI_TRY(open_digest(core, "kai open digest"));
+    KAI_TRY(open_kernels(core));
     HIP_TRY(core, hipEventRecord(core->ev1, core->stream));
     const auto t_enq = tnow();
     HIP_TRY(core, hipStreamSynchronize(core->stream));  // prep's host buffers die with this scope
+    if (digest) KAI_TRY(open_digest(core, "kai open digest behind the kernels"));
     if (prof_open) std::fprintf(stderr, "kai open: free %.2f ms, checks + shared pods %.2f, the snapshot's arrays staged %.2f, host prep %.2f, allocate + enqueue uploads %.2f, wait %.2f | total %.2f ms\n",
                                 ms_between(t_begin, t_freed), ms_between(t_freed, t_shared), ms_between(t_shared, t_staged), ms_between(t_staged, t_prep), ms_between(t_prep, t_enq), ms_between(t_enq, tnow()), ms_between(t_begin, tnow()));
     if (prof_open) std::fprintf(stderr, "kai open: host prep by phase: range checks %.2f, nodes %.2f, pods %.2f, task order %.2f, queues + job lists %.2f, shares + topology %.2f, classes %.2f, batch shape %.2f ms on %d host threads\n",
@@ -186,8 +189,7 @@ int reset_state(kai_core* core) {
       HIP_TRY(core, hipMemsetAsync(KAI_VP(c.ng_mark), 0, (size_t)std::max(c.N, 1) * 4, core->stream)); HIP_TRY(core, hipMemsetAsync(KAI_VP(c.ng_has_alloc), 0, (size_t)std::max(c.N, 1) * 4, core->stream)); }
     if (core->solver_ready) HIP_TRY(core, hipMemsetAsync(c.sv.xr_key, 0xFF, sizeof(int64_t) * ((size_t)c.sv.xr_mask + 1), core->stream));
     HIP_TRY(core, hipMemsetAsync(KAI_VP(c.st), 0, sizeof(EngineState), core->stream));
-    KAI_TRY(launch_open_kernels(core));
-    core->index_stale = false;
+    KAI_TRY(open_kernels(core));
     HIP_TRY(core, hipEventRecord(core->ev1, core->stream));
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     float ms = 0; HIP_TRY(core, hipEventElapsedTime(&ms, core->ev0, core->ev1));

@@ -1,5 +1,6 @@
 // sim_session.hpp — TEST INFRASTRUCTURE: a session of the host simulation as an object.  The engine's control flow (kai::Engine<>, the same header the gfx950 kernel instantiates)
-// on a serial node scanner (HostBackend), the batch path's kernels on the lock-step emulator (HostLauncher), and struct SimSession: open / action / read-backs / snapshot_state.
+// on a serial node scanner (HostBackend), the batch path's kernels (HostLauncher) and the session-open, action-init and drain kernels (SimOpenLauncher: the library's own launch
+// sequences of kai_open_kernels.hpp) on the lock-step emulator, and struct SimSession: open / action / read-backs / snapshot_state.
 // host_sim.cpp runs whole cycles on it (kai_hostsim_run); a harness for an entry point that acts on an open session (ops_apply_sim.cpp, stale_gangs_sim.cpp) opens one, runs
 // actions, makes its calls on ctx() between them and reads back.  Include it FIRST: the two macros below must stand in front of the engine's headers.  One translation unit per
 // library (the switches the kai_hostsim_set_* exports write are statics of this header).  NOT a CPU fallback: libkai_core never contains any of it.
@@ -18,6 +19,7 @@ static int g_dom_lanes_min = std::getenv("KAI_HOSTSIM_DOM_MIN") ? std::atoi(std:
 
 #include "../../kai-scheduler_amd/csrc/kai_host_prep.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_ctx_build.hpp"
+#include "../../kai-scheduler_amd/csrc/kai_open_kernels.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_batch_kernels.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_batch_driver.hpp"
 #include "../../kai-scheduler_amd/csrc/kai_victim_shard.hpp"
@@ -295,6 +297,25 @@ struct HostLauncher {
     int zero(void* dst, size_t n) { std::memset(dst, 0, n); return 0; }
 };
 
+// the session-open, action-init and drain kernels on the emulator (the Launcher of kai_open_kernels.hpp's sequences).  The emulator is one object: calling thread only.
+struct SimOpenLauncher {
+    template <class P> void fill32(P p, int byte, size_t n) { std::memset((void*)p, byte, n * 4); }
+    void node_accounting(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { node_accounting_body(c); }); }
+    void pod_accounting_reset(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { pod_accounting_reset_body(c); }); }
+    void node_accounting_shared(int g, int b, const KaiCtx& c, const int32_t* np_off, const int32_t* np_pods) { kw::launch(g, b, 0, [&] { node_accounting_shared_body(c, np_off, np_pods); }); }
+    void total_nodes(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { total_nodes_body(c); }); }
+    void total_foreign(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { total_foreign_body(c); }); }
+    void job_usage(int g, int b, const KaiCtx& c, double* jsum) { kw::launch(g, b, 0, [&] { job_usage_body(c, jsum); }); }
+    void leaf_usage(int g, int b, const KaiCtx& c, const double* jsum) { kw::launch(g, b, 0, [&] { leaf_usage_body(c, jsum); }); }
+    void tree_usage(int g, int b, const KaiCtx& c, const int32_t* h_off, const int32_t* h_nodes, int n_h) { kw::launch(g, b, 0, [&] { tree_usage_body(c, h_off, h_nodes, n_h); }); }
+    void fair_share_level(int g, int b, const KaiCtx& c, const int32_t* lvl_parents, int first, int count, double* weight, double* rem_amt, uint8_t* rem_has) { kw::launch(g, b, 0, [&] { fair_share_level_body(c, lvl_parents, first, count, weight, rem_amt, rem_has); }); }
+    void qnode_static(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { qnode_static_body(c); }); }
+    void index_build(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { index_build_body(c); }); }
+    void job_init(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { job_init_body(c); }); }
+    void leaf_init(int g, int b, const KaiCtx& c) { kw::launch(g, b, 0, [&] { leaf_init_body(c); }); }
+    void drain(int g, int b, const KaiCtx& c, const int32_t* slot_queue) { kw::launch(g, b, 0, [&] { drain_body(c, slot_queue); }); }
+};
+
 template <class T> T* own(std::vector<std::vector<char>>& pool, size_t n) {
     pool.emplace_back(std::max<size_t>(n, 1) * sizeof(T), 0);
     return reinterpret_cast<T*>(pool.back().data());
@@ -336,9 +357,9 @@ struct SimSession {
     const kai_config* cfg = nullptr; const kai_snapshot_soa* s = nullptr;
     SharedPods sp;  // shared GPUs in the engine: one GPU memory size for the whole cluster (the queue-capacity step stays node independent)
     HostPrep prep; bool shared = false; int n_actions_total = 1; bool batch_path = true;
-    std::vector<std::vector<char>> pool; KaiCtx c{}; OpenAux aux;  // (aux: the arguments of the real open kernels; the serial twins below read prep instead)
+    std::vector<std::vector<char>> pool; KaiCtx c{}; OpenAux aux;  // (aux: the open's arrays outside the context — arguments of the open kernels and of the drain)
     std::vector<SimArena::Rec> recs;  // every array of the context, as kai_core::allocs lists them
-    std::string* digest_out = nullptr;  // set before open: what the builder put into every array, before the serial twins of the open kernels run — the lines kai_session_open prints under KAI_OPEN_DIGEST
+    std::string* digest_out = nullptr;  // set before open: what the builder put into every array, and what the open's kernels left in them — the two sets of lines kai_session_open prints under KAI_OPEN_DIGEST
     HostBackend be; std::optional<Engine<HostBackend>> eng;  // the one engine that lives across the session's actions
     struct Rep { std::vector<std::vector<char>> pool; KaiCtx c{}; OpenAux aux; };
     std::vector<Rep> reps;  // further engines of a victim action: replicas of the context, of identical layout
@@ -359,14 +380,18 @@ struct SimSession {
         if (s->pod_flags) { std::vector<int32_t> cnt; flag_legacy_mig_nodes(s, prep, cnt); }
         if (int rc = build_ctx(pool, c, aux, &recs)) return rc;
         if (!lean_equals_full()) return KAI_ERR_STATE;
-        if (digest_out) for (const SimArena::Rec& a : recs) {
-            uint64_t f = 1469598103934665603ull; for (size_t i = 0; i < a.bytes; i++) { f ^= (unsigned char)a.base[i]; f *= 1099511628211ull; }
-            char ln[96]; std::snprintf(ln, sizeof ln, "kai open digest: field %zu bytes %zu fnv %016llx\n", a.field_off, a.bytes, (unsigned long long)f); *digest_out += ln;
-        }
+        digest("kai open digest");
         t0 = std::chrono::steady_clock::now();
-        if (int rc = derive_open_state()) return rc;
+        if (int rc = open_kernels()) return rc;
+        digest("kai open digest behind the kernels");
         eng.emplace(c, be);
         return KAI_OK;
+    }
+    void digest(const char* prefix) const {
+        if (digest_out) for (const SimArena::Rec& a : recs) {
+            uint64_t f = 1469598103934665603ull; for (size_t i = 0; i < a.bytes; i++) { f ^= (unsigned char)a.base[i]; f *= 1099511628211ull; }
+            char ln[128]; std::snprintf(ln, sizeof ln, "%s: field %zu bytes %zu fnv %016llx\n", prefix, a.field_off, a.bytes, (unsigned long long)f); *digest_out += ln;
+        }
     }
     // kai_session_open does not SEND what a snapshot holds as constants (kai_ctx_build.hpp: the shared-GPU model's per-pod arrays without shared-GPU requests and MIG rows, the
     // identity tables of a snapshot without sub-group trees, "no nominated node") — it writes them where they are read.  That they are what would have been sent is checked here on
@@ -396,68 +421,11 @@ struct SimSession {
         return 0;
     }
 
-    // ---- serial twins of the session-open kernels (kai_session_open.hpp launch_open_kernels), in their order; k_... names the kernel a block restates
-    int node_accounting() {
-        const int N = c.N, P = c.P, R = c.R;
-        std::vector<int> acct(P); for (int p = 0; p < P; p++) acct[p] = p;
-        if (shared) std::sort(acct.begin(), acct.end(), [&](int a, int b) { return s->pod_uid_rank[a] < s->pod_uid_rank[b]; });  // AddTasksToNode order of the fixtures (nodes_fake/nodes.go:289-302): the shared-GPU guards are order sensitive
-        if (shared) std::memset(c.ng_id, 0xFF, sizeof(int32_t) * (size_t)N * KAI_GMAX);  // as launch_open_kernels resets the group tables
-        for (int p = 0; p < P; p++) c.p_on_node[p] = -1;
-        for (int pi = 0; pi < P; pi++) {  // k_node_accounting
-            const int p = acct[pi];
-            int st = c.p_status[p], n = c.p_node[p];
-            if (!st_active_used(st) || n < 0 || n >= N) continue;
-            c.p_on_node[p] = n; c.p_on_node_status[p] = st; c.p_accepted[p] = 1;
-            if (shared && c.p_shared[p] && c.p_group[p] >= 0) { c.p_on_group[p] = c.p_group[p]; }
-            for (int r = 0; r < R; r++) {
-                if (shared && r == KAI_RES_GPU && c.p_shared[p]) continue;
-                double v = c.p_req[(size_t)r * P + p]; if (v == 0) continue; size_t i = (size_t)r * N + n;
-                c.n_used[i] += v;
-                if (st == KAI_POD_RELEASING) { c.n_rel[i] += v; c.n_idle[i] -= v; } else if (st == KAI_POD_PIPELINED) c.n_rel[i] -= v; else c.n_idle[i] -= v;
-            }
-            if (shared && c.p_shared[p] && c.p_on_group[p] >= 0) { SgNode g{c, n}; if (!g.add(st, c.p_mem[p], c.p_on_group[p])) return KAI_ERR_UNSUPPORTED; }
-        }
-        if (shared) for (int n = 0; n < N; n++) { SgNode g{c, n}; g.refit(); }  // as k_node_accounting_shared
-        return KAI_OK;
-    }
-    int derive_open_state() {
-        const int N = c.N, P = c.P, J = c.J, Q = c.Q, R = c.R;
-        if (int rc = node_accounting()) return rc;
-        if (c.plugins & KAI_PLUGIN_PROPORTION) {  // k_total_nodes + k_total_foreign
-            for (int n = 0; n < N; n++) {
-                uint32_t f = c.n_flags[n]; if (f & KAI_NODE_NOT_READY) continue;
-                bool ignore = c.restrict_nodes && !(f & KAI_NODE_GPU_WORKER);
-                c.st->total[0] += c.n_alloc[(size_t)KAI_RES_CPU * N + n]; c.st->total[1] += c.n_alloc[(size_t)KAI_RES_MEM * N + n];
-                if (!ignore) { c.st->total[2] += c.n_alloc[(size_t)KAI_RES_GPU * N + n]; if (c.mig_on) for (int r = KAI_RES_PODS + 1; r < R; r++) if (c.res_mig_g[r] > 0) c.st->total[2] += (double)c.res_mig_g[r] * c.n_alloc[(size_t)r * N + n]; }
-            }
-            for (int p = 0; p < P; p++) {
-                if (!(c.p_flags[p] & KAI_POD_FOREIGN_SCHEDULER)) continue;
-                int n = c.p_on_node[p]; if (n < 0 || !st_active_used(c.p_on_node_status[p]) || (c.n_flags[n] & KAI_NODE_NOT_READY)) continue;
-                c.st->total[0] -= c.p_req[(size_t)KAI_RES_CPU * P + p]; c.st->total[1] -= c.p_req[(size_t)KAI_RES_MEM * P + p]; c.st->total[2] -= c.quota_on ? c.p_quota_gpu[p] : c.p_req[(size_t)KAI_RES_GPU * P + p];
-            }
-        }
-        for (int j = 0; j < J; j++) {  // k_job_usage + k_leaf_usage
-            double al[3] = {0, 0, 0}, rq[3] = {0, 0, 0}, ja[3] = {0, 0, 0}; int pending = 0;
-            for (int i = 0; i < c.j_n_pods[j]; i++) {
-                int p = c.j_first_pod[j] + i, st = c.p_status[p], ps = c.p_podset[p];
-                if (st_active_allocated(st)) c.s_active_alloc[ps]++;
-                if (st_active_used(st)) c.s_active_used[ps]++;
-                if (st_alive(st)) c.s_alive[ps]++;
-                if (st == KAI_POD_GATED) c.s_gated[ps]++;
-                if (st == KAI_POD_PIPELINED) c.s_pipelined[ps]++;
-                if (st == KAI_POD_PENDING) pending++;
-                double q[3] = {c.p_req[(size_t)KAI_RES_CPU * P + p], c.p_req[(size_t)KAI_RES_MEM * P + p], c.p_req[(size_t)KAI_RES_GPU * P + p]};
-                const double qa = c.quota_on ? c.p_acc_gpu[p] : q[2], qp = c.quota_on ? c.p_pend_gpu[p] : q[2], qq = c.quota_on ? c.p_quota_gpu[p] : q[2];  // accepted quota / pending weight / request quota (gpu-memory, MIG)
-                if (st_allocated(st)) { for (int k = 0; k < 3; k++) ja[k] += k == 2 ? qq : q[k]; if (c.p_accepted[p]) for (int k = 0; k < 3; k++) { const double v = k == 2 ? qa : q[k]; al[k] += v; rq[k] += v; } }
-                else if (st == KAI_POD_PENDING) for (int k = 0; k < 3; k++) rq[k] += k == 2 ? qp : q[k];
-            }
-            c.j_n_pending[j] = pending;
-            for (int k = 0; k < 3; k++) c.j_allocated[(size_t)j * 4 + k] = ja[k];
-            if ((c.plugins & KAI_PLUGIN_PROPORTION) && c.j_queue[j] >= 0) for (int k = 0; k < 3; k++) {
-                QShare& x = c.q_share[(size_t)c.j_queue[j] * 3 + k];
-                x.allocated += al[k]; x.request += rq[k]; if (!c.j_preempt[j]) x.allocated_np += al[k];
-            }
-        }
+    // the session-open kernels in kai_session_open's sequence (kai_open_kernels.hpp open_drive), on the calling thread; in two halves only for the harness-only step between them
+    int open_kernels() {
+        const int P = c.P, J = c.J, Q = c.Q;
+        SimOpenLauncher l; const OpenShape shape{prep.n_levels, prep.lvl_off.data(), prep.n_heights, (uint32_t)c.plugins, shared};
+        open_usage_drive(l, c, aux, shape);
         // With fraction pods the queue sums are sums of non-integers and their last bit depends on the order of addition.  The device kernels roll pods
         // up job by job and queue by queue; the reference walks pod by pod up the ancestry in Go-map order (proportion.go:347-401), the oracle in (job,
         // status, pod) order.  KAI_HOSTSIM_POD_ORDER_SUMS=1 makes this harness add in the oracle's order, which takes the order of addition out of a
@@ -480,24 +448,10 @@ struct SimSession {
                 }
             }
         }
-        if (c.plugins & KAI_PLUGIN_PROPORTION) {
-            if (!pod_order_sums) for (int i = 0; i < Q; i++) {  // k_tree_usage
-                int q = prep.depth_order[i], par = c.q_parent[q]; if (par < 0) continue;
-                for (int k = 0; k < 3; k++) { QShare& x = c.q_share[(size_t)q * 3 + k]; QShare& d = c.q_share[(size_t)par * 3 + k]; d.allocated += x.allocated; d.allocated_np += x.allocated_np; d.request += x.request; }
-            }
-            std::vector<double> weight((size_t)3 * std::max(Q, 1)), rem_amt((size_t)3 * std::max(Q, 1)); std::vector<uint8_t> rem_has((size_t)3 * std::max(Q, 1));
-            for (int l = 0; l < prep.n_levels; l++) for (int t = prep.lvl_off[l] * 3; t < prep.lvl_off[l + 1] * 3; t++) {  // k_fair_share
-                int par = prep.lvl_parents[t / 3], k = t % 3;
-                double total = par == Q ? c.st->total[k] : c.q_share[(size_t)par * 3 + k].fair;
-                divide_sibling_set(c, c.q_children + c.q_child_off[par], c.q_child_off[par + 1] - c.q_child_off[par], k, total, c.k_value,
-                                   weight.data() + (size_t)k * Q, rem_amt.data() + (size_t)k * Q, rem_has.data() + (size_t)k * Q);
-            }
-        }
-        for (int q = 0; q < Q; q++) qnode_init(c, q, 0);  // k_qnode_static: the event handlers walk the tree's parents, also before the first action has filled it
-        rebuild_index();  // k_index_build
-        return KAI_OK;
+        open_shares_drive(l, c, aux, shape);
+        return c.st->fault ? KAI_ERR_UNSUPPORTED : KAI_OK;  // (a node's shared-GPU groups did not take its pods: node_accounting_shared_body)
     }
-    void rebuild_index() { if (c.use_index) for (int b = 0; b < c.NB; b++) for (int k = 0; k < c.C; k++) HostBackend::build_block(c, k, b); }
+    void rebuild_index() { SimOpenLauncher l; index_drive(l, c); }
     // A call from outside the actions wrote pods into the session (kai_ops_apply, kai_stale_gang_eviction): what kai_core.hip does on the host behind their kernels
     void state_written(bool non_allocate) { index_stale = true; if (non_allocate) c.fast_ok = 0; }
 
@@ -513,14 +467,7 @@ struct SimSession {
         return KAI_OK;
     }
     void action_init() {
-        const int J = c.J, Q = c.Q;
-        if (index_stale) { rebuild_index(); index_stale = false; }  // as kai_action_execute: the bucket fill keeps the sets current, not the class index
-        for (int j = 0; j < J; j++) { c.j_state[j] = job_init_state(c, j); if (c.j_state[j] != 3 && c.j_n_ps[j] <= 64) eng->ensure_tta(j, true); }  // k_job_init
-        for (int q = 0; q < Q; q++) {                                      // k_leaf_init
-            int b = c.q_job_off[q], e = c.q_job_off[q + 1], cnt = 0; c.lq_side_len[q] = 0;
-            for (int x = b; x < e; x++) { int j = c.jobs_static[x]; int st = c.j_state[j]; if (st == 0) c.lq_sorted[b + cnt++] = j; else if (st != 3) eng->leaf_push(q, j); }
-            c.lq_cur[q] = 0; c.lq_end[q] = cnt; qnode_init(c, q, cnt + c.lq_side_len[q]);
-        }
+        SimOpenLauncher l; action_init_drive(l, c, index_stale);  // as kai_action_execute: the bucket fill keeps the sets current, not the class index
         if (std::getenv("KAI_HOSTSIM_PS")) { int ps = std::atoi(std::getenv("KAI_HOSTSIM_PS")); std::fprintf(stderr, "host_sim: before action %d podset %d active_alloc %d used %d alive %d pipelined %d\n", c.action, ps, c.s_active_alloc[ps], c.s_active_used[ps], c.s_alive[ps], c.s_pipelined[ps]); }
         if (c.st->non_allocate_commits) c.fast_ok = 0;  // as kai_action_execute does after every action
     }
@@ -593,18 +540,7 @@ struct SimSession {
         }
         return KAI_OK;
     }
-    void drain() {                                                         // k_drain
-        if (c.st->drain_pending) {
-            for (int x = 0; x < c.J; x++) {
-                int q = prep.slot_queue[x]; if (q < 0) continue; int pos = x - c.q_job_off[q];
-                int64_t att = 0, dec = 0, rb = 0;
-                if (pos >= c.lq_cur[q] && pos < c.lq_end[q]) eng->drain_job(c.lq_sorted[x], att, dec, rb);
-                if (pos < c.lq_side_len[q]) eng->drain_job(c.lq_side[x], att, dec, rb);
-                c.st->jobs_attempted += att; c.st->decisions += dec; c.st->rollbacks += rb; c.st->drained_jobs += att; c.st->drained_decisions += dec;
-            }
-            c.st->drain_pending = 0;
-        }
-    }
+    void drain() { SimOpenLauncher l; drain_drive(l, c, aux); c.st->drain_pending = 0; }  // (the library's scalars start every action from zero; this harness keeps one EngineState for the cycle)
 
     // ---- behind the last action: the engine's verdict, then the read-backs (nodes in the caller's indices: prep.perm is engine node -> caller's index, prep.rank_of its inverse)
     int finish() const {
