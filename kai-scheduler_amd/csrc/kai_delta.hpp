@@ -9,6 +9,8 @@
 // mapping the caller's node indices through the name-rank permutation.  k_class_remap re-labels every pod's scan class when the class table changed.
 // k_apply_rows scatters the rows (RowsView: further arrays of the same buffer) into the QShare baseline, the queues' priorities and min-runtime settings and the jobs'
 // last start times; nothing on the host or the device is derived from those except what kai_session_reset's kernels compute again after every scatter.
+// The CPU suite runs none of these kernels (its stand-in runtime launches nothing, the emulator does not take them): tests/test_gpu_update_chains.py holds them, and the
+// host's bookkeeping around them, to a fresh open across chains of updates (tests/update_chains.py), at delta sizes on both sides of a workgroup's 256 threads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,8 @@
 """kai_session_update without a GPU: the library's host side (kai_core.hip compiled host-only and linked with tests/host_sim/fake_hip.cpp, as
 tests/test_open_uploads.py does: device memory is host memory, kernels do nothing) checks the delta's arguments and the call order before anything is
-written, and a refusal leaves the session open and unchanged.  The delta helper (abi.apply_delta) builds the snapshot S' that kai_session_open accepts."""
+written, and a refusal leaves the session open and unchanged.  The delta helper (abi.apply_delta) builds the snapshot S' that kai_session_open accepts.
+What an update computes is not checked here (the gather returns nothing under the stand-in runtime): tests/test_update_chains.py checks the chains of updates in
+tests/update_chains.py as inputs, tests/test_gpu_update_chains.py walks them on the MI355X."""
 import json
 import os
 import subprocess
