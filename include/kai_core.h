@@ -582,6 +582,42 @@ int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params,
                             int64_t* job_stale_since_ns /* [n_jobs] in/out, 0 = nil */, uint8_t* job_stale_out /* [n_jobs] or NULL: StalenessInfo.Stale */,
                             kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, kai_stale_result* result /* may be NULL */);
 
+/* replaces: the reflectjoborder plugin's computation (plugins/reflectjoborder/reflect_job_order.go:41-66, served as /get-job-order): in what order are the
+ * queued jobs served, and where does a job stand in its queue?
+ *  - order_out[0 .. *n_out) is the sequence of PopNextJob results (actions/utils/job_order_by_queue.go:61-89) of a JobsOrderByQueues built with FilterNonPending,
+ *    FilterUnready (actions/utils/input_jobs.go:21-68), the given depth and VictimQueue = false over all jobs, at the session's CURRENT state: after whatever
+ *    actions, kai_ops_apply or kai_stale_gang_eviction calls ran — shares, pod statuses and elastic state as they are now.  Nothing is allocated between pops.
+ *    params->depth: 0 = kai_config.queue_depth[KAI_ACTION_ALLOCATE] (what reflectjoborder takes, ssn.GetJobsDepth), -1 = infinite, > 0 = that many jobs per leaf queue.
+ *  - job_pos_out[j] (may be NULL) is job j's position in that sequence (GlobalOrder); job_queue_pos_out[j] (may be NULL) its position among the jobs of its own
+ *    leaf queue, QueueOrder[job.Queue] of the reference (:61-62): what a "position in queue" display shows.  Both are -1 for a job that is not in the order.
+ *  - result (may be NULL): n_ordered = *n_out; path (KAI_JOB_ORDER_PATH_*) = what ordered; n_leaves = leaf queues with a job in the order (the keys of QueueOrder).
+ * The call changes nothing: kai_pod_states, kai_node_states, kai_queue_shares, kai_action_stats_get, the answers of kai_best_node(s) / kai_ordered_nodes and every
+ * later action, kai_ops_apply or kai_session_update* are as if it had not happened.  It re-derives what every action's own init re-derives before anything reads
+ * it: the jobs' filter / elastic state (j_state), the tasks-to-allocate chunks where their cache is invalid (job_info.go:253-256 invalidates it with every status
+ * change; the chunk is a function of the current state), the leaves' sorted regions and side heaps and the records and heaps of the job-order tree.  Nothing
+ * reads those between actions: kai_action_execute rebuilds them (k_job_init, k_leaf_init, Engine::init_jobs_order) before its first pop.
+ * Two paths, the same order.  Chip-wide (KAI_JOB_ORDER_PATH_WIDE): no pop changes any share, so the order is one bottom-up pass of scans and merges over the queue
+ * tree, the allocate action's plan with constant shares — taken when the siblings' static order (queue_order.go:214-240) is strict in every sibling set, the tree has
+ * at most 16 levels, the proportion plugin orders the queues and every queued job is below minAvailable with a valid tasks-to-allocate chunk; the jobs need not be
+ * plain gangs and a finite depth does not disqualify.  Otherwise (KAI_JOB_ORDER_PATH_ENGINE) one lane walks the engine's own job-order tree until it is empty.
+ * A session with shared-GPU requests is not refused: nothing is allocated.  No queued job: KAI_OK, *n_out = 0, path KAI_JOB_ORDER_PATH_NONE.
+ * Refusals, all decided before the first device call, leave every output untouched:
+ *  - KAI_ERR_INVALID_ARG: a wrong version, unknown flag bits, non-zero pad, depth < -1, NULL params / n_out, NULL order_out with cap > 0, a negative cap;
+ *  - KAI_ERR_STATE: no open session;  KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1).
+ * KAI_ERR_CAPACITY: cap is below the number of ordered jobs, known once the device has counted them; *n_out holds the number needed (n_jobs always suffices), the
+ * other outputs are untouched. */
+#define KAI_JOB_ORDER_VERSION 1u
+#define KAI_JOB_ORDER_ENGINE_PATH 0x1u   /* take the heap walk even where the chip-wide path qualifies (tests, A/B) */
+#define KAI_JOB_ORDER_PATH_NONE 0
+#define KAI_JOB_ORDER_PATH_WIDE 1
+#define KAI_JOB_ORDER_PATH_ENGINE 2
+typedef struct kai_job_order_params { uint32_t version; uint32_t flags; int32_t depth; int32_t pad; } kai_job_order_params;
+typedef struct kai_job_order_result { int32_t n_ordered; int32_t path; int32_t n_leaves; int32_t pad; } kai_job_order_result;
+int kai_job_order(kai_core* core, const kai_job_order_params* params,
+                  int32_t* order_out, int32_t cap, int32_t* n_out,          /* job indices in pop order */
+                  int32_t* job_pos_out /* [n_jobs] or NULL */, int32_t* job_queue_pos_out /* [n_jobs] or NULL */,
+                  kai_job_order_result* result /* may be NULL */);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

@@ -250,6 +250,20 @@ class KaiStaleResult(C.Structure):
     _fields_ = [("stale_jobs", C.c_int32), ("expired_jobs", C.c_int32), ("n_ops", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
 
 
+JOB_ORDER_VERSION, JOB_ORDER_ENGINE_PATH = 1, 0x1  # KAI_JOB_ORDER_VERSION, KAI_JOB_ORDER_ENGINE_PATH
+JOB_ORDER_PATH_NONE, JOB_ORDER_PATH_WIDE, JOB_ORDER_PATH_ENGINE = 0, 1, 2  # kai_job_order_result.path
+
+
+class KaiJobOrderParams(C.Structure):
+    """kai_job_order_params (include/kai_core.h): kai_job_order's flags and queue depth (0: the config's allocate depth, -1: infinite, > 0: jobs per leaf queue)."""
+    _fields_ = [("version", C.c_uint32), ("flags", C.c_uint32), ("depth", C.c_int32), ("pad", C.c_int32)]
+
+
+class KaiJobOrderResult(C.Structure):
+    """kai_job_order_result (include/kai_core.h): the ordered jobs, the path (JOB_ORDER_PATH_*) that ordered them, the leaf queues with a job in the order."""
+    _fields_ = [("n_ordered", C.c_int32), ("path", C.c_int32), ("n_leaves", C.c_int32), ("pad", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -128,6 +128,8 @@ def load_library(path: str = LIB_PATH):
     lib.kai_ops_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiApplyResult)]
     lib.kai_stale_gang_eviction.argtypes = [C.c_void_p, C.POINTER(abi.KaiStaleParams), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(abi.KaiOp), C.c_int64,
                                             C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
+    lib.kai_job_order.argtypes = [C.c_void_p, C.POINTER(abi.KaiJobOrderParams), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(abi.KaiJobOrderResult)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -377,6 +379,19 @@ class Session:
         self.core._check(self.core.lib.kai_stale_gang_eviction(self.core.handle, C.byref(params), since.ctypes.data_as(C.POINTER(C.c_int64)), stale.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                                ops.ctypes.data_as(C.POINTER(abi.KaiOp)), P, C.byref(n), C.byref(res)))
         return ops[:n.value].copy(), since[:J], stale[:J].astype(bool), res
+
+    def job_order(self, depth: int = 0, engine_path: bool = False):
+        """kai_job_order: the pop order of the queued jobs at the session's current state (what the reflectjoborder plugin serves), nothing allocated between pops.
+        depth: 0 = the config's allocate queue depth, -1 = infinite, > 0 = that many jobs per leaf queue; engine_path: the heap walk even where the chip-wide path
+        qualifies.  Returns (order, job_pos, job_queue_pos, result): the job indices in pop order, every job's position in it and among the jobs of its own leaf queue
+        (-1: not in the order), and the kai_job_order_result."""
+        J = self.snap.n_jobs
+        order, pos, qpos = np.zeros(max(J, 1), np.int32), np.full(max(J, 1), -1, np.int32), np.full(max(J, 1), -1, np.int32)
+        n, res = C.c_int32(0), abi.KaiJobOrderResult()
+        params = abi.KaiJobOrderParams(abi.JOB_ORDER_VERSION, abi.JOB_ORDER_ENGINE_PATH if engine_path else 0, int(depth), 0)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self.core._check(self.core.lib.kai_job_order(self.core.handle, C.byref(params), ip(order), J, C.byref(n), ip(pos), ip(qpos), C.byref(res)))
+        return order[:n.value].copy(), pos[:J], qpos[:J], res
 
     def gpu_groups(self):
         """PodInfo.GPUGroups[0] of the active fraction pods (-1 elsewhere): kai_pod_gpu_groups."""

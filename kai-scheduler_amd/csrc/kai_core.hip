@@ -448,6 +448,107 @@ int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params, int6
     return KAI_OK;
 }
 
+}  // extern "C"
+
+// kai_job_order's kernels for jo_drive (kai_job_order.hpp); pin: where the head lands in the handle's staging.  KAI_JOB_ORDER_PROF: every launch between two events and waited
+// for, the milliseconds per kernel summed over the call and printed (tools/job_order_timing.py reads the line).  (A member template: outside the extern "C" block.)
+struct JoLauncher {
+    kai_core* core; unsigned char* pin; bool prof = false; std::vector<std::pair<const char*, float>> spent;
+    static dim3 g(int n) { return dim3((unsigned)n); }
+    template <class F> void run(const char* name, F&& launch) {
+        if (!prof) { launch(); return; }
+        (void)hipEventRecord(core->ev0, core->stream); launch(); (void)hipEventRecord(core->ev1, core->stream); (void)hipEventSynchronize(core->ev1);
+        float ms = 0; if (hipEventElapsedTime(&ms, core->ev0, core->ev1) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+        for (auto& e : spent) if (e.first == name) { e.second += ms; return; }
+        spent.push_back({name, ms});
+    }
+    void report(int path, int n) const {
+        if (!prof) return;
+        std::fprintf(stderr, "kai job order: path %d ordered %d |", path, n);
+        for (const auto& e : spent) std::fprintf(stderr, " %s %.4f", e.first, e.second);
+        std::fprintf(stderr, " ms\n");
+    }
+    void job_init(int n, int b, const KaiCtx& c) { run("k_job_init", [&] { hipLaunchKernelGGL(k_job_init, g(n), g(b), 0, core->stream, c); }); }
+    void leaf_init(int n, int b, const KaiCtx& c) { run("k_leaf_init", [&] { hipLaunchKernelGGL(k_leaf_init, g(n), g(b), 0, core->stream, c); }); }
+    void qualify(int n, int b, const KaiCtx& c, const JoArgs& a) { run("k_jo_qualify", [&] { hipLaunchKernelGGL(k_jo_qualify, g(n), g(b), 0, core->stream, c, a); }); }
+    void static_rank(int n, int b, const KaiCtx& c) { run("k_batch_static_rank", [&] { hipLaunchKernelGGL(k_batch_static_rank, g(n), g(b), 0, core->stream, c); }); }
+    void static_check(int n, int b, const KaiCtx& c) { run("k_batch_static_check", [&] { hipLaunchKernelGGL(k_batch_static_check, g(n), g(b), 0, core->stream, c); }); }
+    void plan_setup(int n, int b, const KaiCtx& c, RoundParams rp) { run("k_plan_setup", [&] { hipLaunchKernelGGL(k_plan_setup, g(n), g(b), 0, core->stream, c, rp); }); }
+    void leaf(int n, int b, const KaiCtx& c, const JoArgs& a) { run("k_jo_leaf", [&] { hipLaunchKernelGGL(k_jo_leaf, g(n), g(b), 0, core->stream, c, a); }); }
+    void plan_rank(int n, int b, const KaiCtx& c, RoundParams rp) { run("k_plan_rank", [&] { hipLaunchKernelGGL(k_plan_rank, g(n), g(b), 0, core->stream, c, rp); }); }
+    void keys(int n, int b, const KaiCtx& c, const JoArgs& a, RoundParams rp) { run("k_jo_keys", [&] { hipLaunchKernelGGL(k_jo_keys, g(n), g(b), 0, core->stream, c, a, rp); }); }
+    void scan(int n, int b, const KaiCtx& c, RoundParams rp) { run("k_jo_scan", [&] { hipLaunchKernelGGL(k_jo_scan, g(n), g(b), 0, core->stream, c, rp); }); }
+    void emit(int n, int b, const KaiCtx& c, const JoArgs& a) { run("k_jo_emit", [&] { hipLaunchKernelGGL(k_jo_emit, g(n), g(b), 0, core->stream, c, a); }); }
+    int engine(const KaiCtx& c, const JoArgs& a) { run("k_jo_engine", [&] { hipLaunchKernelGGL(k_jo_engine, dim3(1), dim3(64), 0, core->stream, c, a); }); return KAI_OK; }
+    int read_head(JoHead& hd, const JoArgs& a) {
+        HIP_TRY(core, hipGetLastError());
+        HIP_TRY(core, hipMemcpyAsync(pin, (const void*)a.head, sizeof(JoHead), hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+        std::memcpy(&hd, pin, sizeof(JoHead));
+        return KAI_OK;
+    }
+};
+
+extern "C" {
+
+int kai_job_order(kai_core* core, const kai_job_order_params* params, int32_t* order_out, int32_t cap, int32_t* n_out,
+                  int32_t* job_pos_out, int32_t* job_queue_pos_out, kai_job_order_result* result) {
+    // every refusal before the first device call and before the first write to the caller's arrays
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (!params || !n_out) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: params / n_out is NULL");
+    if (params->version != KAI_JOB_ORDER_VERSION) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: wrong params version");
+    if (params->flags & ~KAI_JOB_ORDER_ENGINE_PATH) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: unknown flag bits");
+    if (params->pad != 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: pad is not zero");
+    if (params->depth < -1) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: depth below -1");
+    if (cap < 0 || (cap > 0 && !order_out)) return fail(core, KAI_ERR_INVALID_ARG, "kai_job_order: a negative capacity, or order_out is NULL");
+    if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_job_order: a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    const KaiCtx& c = core->ctx;
+    const int J = c.J, Q = c.Q, n_heights = core->prep.n_heights;
+    int depth = params->depth == 0 ? core->cfg.queue_depth[KAI_ACTION_ALLOCATE] : params->depth;
+    if (depth < 0) depth = 0;  // (infinite)
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
+    const size_t pool = jo_pool(J, Q, n_heights);
+    const JoLayout L((size_t)J, (size_t)Q, (size_t)n_heights, pool);
+    bool grew = false;
+    KAI_TRY(reserve(core, core->jo_dev, L.end, L.end + L.end / 4, &grew));
+    if (grew) HIP_TRY(core, hipMemsetAsync(core->jo_dev.p, 0, core->jo_dev.bytes, core->stream));  // (the pools' indices are checked where they are read; zeros rather than what the memory held)
+    const size_t pin_need = L.down_end + sizeof(JoHead);  // [what is sent, and later what comes back][the head between the launches]
+    KAI_TRY(reserve(core, core->jo_pin, pin_need, std::max<size_t>(pin_need + pin_need / 4, (size_t)1 << 16)));
+    unsigned char* h = core->jo_pin.p; unsigned char* d = core->jo_dev.p;
+    // ---- one upload: the zeroed head and the queue tree's tables (heights, nodes by height)
+    std::memset(h, 0, L.up_end);
+    std::memcpy(h + L.q_height, core->prep.q_height.data(), (size_t)(Q + 1) * 4);
+    std::memcpy(h + L.h_off, core->prep.h_off.data(), (size_t)(n_heights + 1) * 4);
+    std::memcpy(h + L.h_nodes, core->prep.h_nodes.data(), (size_t)(Q + 1) * 4);
+    HIP_TRY(core, hipMemcpyAsync(d, h, L.up_end, hipMemcpyHostToDevice, core->stream));
+    const KaiCtx cj = jo_bind_ctx(c, d, L, n_heights, pool, depth);
+    const JoArgs a = jo_bind_args(c, d, L, pool);
+    // ---- the init, the qualification behind one small download, the order (jo_drive)
+    JoLauncher launcher{core, h + L.down_end, std::getenv("KAI_JOB_ORDER_PROF") != nullptr};
+    JoHead hd{}; int path = KAI_JOB_ORDER_PATH_NONE;
+    const int rcd = jo_drive(launcher, cj, a, core->shape, jo_wide_session(c, n_heights, pool), depth, params->flags, KAI_JO_WG, hd, path);
+    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[160]; std::snprintf(buf, sizeof buf, "kai_job_order: device fault code %d (engine source line %d)", hd.fault, hd.fault_line); core->err = buf; return rcd; }
+    if (rcd) return rcd;
+    const int n = path == KAI_JOB_ORDER_PATH_NONE ? 0 : hd.n_ordered;
+    launcher.report(path, n);
+    if (n > cap) { *n_out = n; return fail(core, KAI_ERR_CAPACITY, "kai_job_order: cap is below the number of ordered jobs (*n_out holds it)"); }
+    // ---- one download: [.. | order | positions], as far as the caller wants it
+    const bool want_pos = job_pos_out || job_queue_pos_out;
+    const size_t lo = L.order, hi = want_pos && J ? L.down_end : L.order + (size_t)n * 4;
+    if (hi > lo) {
+        HIP_TRY(core, hipMemcpyAsync(h + lo, d + lo, hi - lo, hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+    }
+    if (n) std::memcpy(order_out, h + L.order, (size_t)n * 4);
+    if (job_pos_out && J) std::memcpy(job_pos_out, h + L.pos, (size_t)J * 4);
+    if (job_queue_pos_out && J) std::memcpy(job_queue_pos_out, h + L.qpos, (size_t)J * 4);
+    *n_out = n;
+    if (result) { result->n_ordered = n; result->path = path; result->n_leaves = n ? hd.n_leaves : 0; result->pad = 0; }
+    return KAI_OK;
+}
+
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap) {
     if (!core) return KAI_ERR_INVALID_ARG;
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");

@@ -26,6 +26,7 @@
 #include "kai_ordered_nodes.hpp"
 #include "kai_ops_apply.hpp"
 #include "kai_stale_gangs.hpp"
+#include "kai_job_order.hpp"
 
 using namespace kai;
 
@@ -108,7 +109,9 @@ struct kai_core {
     HandleBuf oa_pin{true}, oa_dev{false}; size_t oa_pod_cap = 0; std::vector<int32_t> oa_rank; bool oa_rank_ok = false;
     // kai_stale_gang_eviction (kai_stale_gangs.hpp): pinned staging and device scratch, grow, live with the handle; jobs and pod-grid workgroups the scratch's arrays hold
     HandleBuf sg_pin{true}, sg_dev{false}; size_t sg_job_cap = 0, sg_wg_cap = 0;
-    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
+    // kai_job_order (kai_job_order.hpp): pinned staging and device scratch (the call's outputs, the tree tables, the plan's pools), grow, live with the handle
+    HandleBuf jo_pin{true}, jo_dev{false};
+    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
 };
 
 // leave the function with a step's status unless it is KAI_OK; a HIP call's error becomes KAI_ERR_HIP with the call's text in kai_last_error

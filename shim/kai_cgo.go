@@ -43,6 +43,7 @@ import (
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api/podgroup_info"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/api/queue_info"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/framework"
+	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/plugins/reflectjoborder"
 	"github.com/NVIDIA/KAI-scheduler/pkg/scheduler/scheduler_util"
 )
 
@@ -977,6 +978,38 @@ func StaleGangEviction(ssn *framework.Session, gracePeriod time.Duration) bool {
 		pack.fallback = true
 	}
 	return true
+}
+
+// JobOrder: what the reflectjoborder plugin computes in OnSessionOpen (plugins/reflectjoborder/reflect_job_order.go:41-66) — the PopNextJob sequence of a
+// JobsOrderByQueues with FilterNonPending, FilterUnready and the allocate action's queue depth — decided by the device against ITS session state in ONE
+// kai_job_order call, in the plugin's own document shape (GlobalOrder, QueueOrder with id and priority).  depth 0 takes kai_config.queue_depth[allocate], which
+// OnSessionOpen packed from ssn.GetJobsDepth(framework.Allocate).  The call changes nothing on the device, so it may be made at any point of the cycle: in front of
+// the first action it answers what the plugin answers, behind an action where the queue stands now.  Not registered anywhere: a deployment that serves
+// /get-job-order from the device session calls it from its handler.
+// nil: no device session (or `fallback` already set), or a refusal of the entry point: the caller builds the order in Go.
+func JobOrder() *reflectjoborder.ReflectJobOrder {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return nil
+	}
+	pack := current.pack
+	doc := &reflectjoborder.ReflectJobOrder{GlobalOrder: make([]reflectjoborder.JobOrder, 0), QueueOrder: make(map[common_info.QueueID][]reflectjoborder.JobOrder)}
+	if len(pack.jobs) == 0 {
+		return doc
+	}
+	order := make([]C.int32_t, len(pack.jobs)) // n_jobs always suffices
+	params := C.kai_job_order_params{version: C.KAI_JOB_ORDER_VERSION}
+	var n C.int32_t
+	// cgo: the array holds no Go pointers, so it may be passed for the duration of the call
+	if rc := C.kai_job_order(core, &params, &order[0], C.int32_t(len(order)), &n, nil, nil, nil); rc != 0 {
+		return nil
+	}
+	for i := 0; i < int(n); i++ {
+		job := pack.jobs[order[i]]
+		jo := reflectjoborder.JobOrder{ID: job.UID, Priority: job.Priority}
+		doc.GlobalOrder = append(doc.GlobalOrder, jo)
+		doc.QueueOrder[job.Queue] = append(doc.QueueOrder[job.Queue], jo) // pop order filtered by the leaf queue: what job_queue_pos_out indexes
+	}
+	return doc
 }
 
 // replay: the committed operations through the real Statement.  kai_op.stmt numbers the Statements of the action in
