@@ -618,6 +618,70 @@ int kai_job_order(kai_core* core, const kai_job_order_params* params,
                   int32_t* job_pos_out /* [n_jobs] or NULL */, int32_t* job_queue_pos_out /* [n_jobs] or NULL */,
                   kai_job_order_result* result /* may be NULL */);
 
+/* replaces: the SubsetNodesFn of the default tier, the topology plugin's subSetNodesFn (plugins/topology/job_filtering.go:34-112), for MANY jobs, sub-groups or
+ * pod-sets at once: which node sets does the allocate action walk for this gang, and in which order?  The answer comes as bitmap rows that go into
+ * kai_best_nodes / kai_ordered_nodes as nodeset_bitmaps rows unchanged.
+ *  - queries[i] asks what subSetNodesFn(job, subGroup, podSets, tasks, nodeSet) returns at the session's CURRENT state (after whatever actions, kai_ops_apply or
+ *    kai_stale_gang_eviction calls ran).  subGroup: group == -1 and podset == -1: the job's root sub-group set; group >= 0: that SubGroupSet (a group of `job`;
+ *    podset must be -1); podset >= 0: that pod-set with its own constraint (a pod-set of `job`; group must be -1).  A snapshot without groups has the root form only.
+ *    tasks: the job's GetTasksToAllocate chunk with isRealAllocation = true at the current state, restricted to the sub-group (what the allocate action hands
+ *    over).  nodeSet: row `nodeset` of nodeset_bitmaps (the rows and bit convention of kai_best_nodes), -1 = all nodes.
+ *  - answers_out[i]: status (KAI_SUBSET_*); n_sets; first = where the query's n_sets records start in sets_out (records lie in query order: the running sum of
+ *    n_sets); tasks = len(tasks); common_domain = what lowestCommonDomainID chose, in kai_node_set.domain's encoding, KAI_SUBSET_PARENT where the function
+ *    returned before it.
+ *  - sets_out[first + k]: the k-th node set the action tries (sortDomainInfos: deepest level first, tree order inside a level after sortTreeFromRoot).  domain: the
+ *    caller's index into the snapshot's domain table, KAI_SUBSET_ROOT(t) for the root domain of topology t, or KAI_SUBSET_PARENT = "the parent node set as it
+ *    is"; level: the level inside the topology, -1 for a root and for PARENT; allocatable_pods: the domain's AllocatablePods, -1 where representor accounting was
+ *    not used (useRepresentorPodsAccounting false) and for PARENT; n_nodes: the size of the set.
+ *  - bitmaps_out (may be NULL), row first + k: the set's nodes — the domain's nodes that are in the parent set (all of them part of the topology: the valid nodes
+ *    of lowestCommonDomainID) — in the caller's node indices.
+ * The reference's order of decisions is the contract (job_filtering.go:38-111): a topology that does not exist (constraint topology -2): KAI_SUBSET_NO_TOPOLOGY;
+ * no constraint, no topology plugin or no task: one set, KAI_SUBSET_PARENT; a common domain that cannot take the tasks: KAI_SUBSET_NO_FIT (before the level check:
+ * a bad level on a gang that does not fit anyway is NO_FIT); no level given, or a level the topology does not have: KAI_SUBSET_BAD_LEVEL (the function returns an
+ * error); no fitting domain on the relevant levels: KAI_SUBSET_NO_FIT; otherwise the ordered list — restricted to the sub-trees that already hold an active pod
+ * of the sub-group where a required level is set (getRelevantDomainsWithAllocatedPods).
+ * The call changes nothing: kai_pod_states, kai_node_states, kai_queue_shares, kai_action_stats_get, the answers of kai_best_node(s) / kai_ordered_nodes /
+ * kai_job_order and every later action, kai_ops_apply or kai_session_update* are as if it had not happened.  It re-derives what every action's own init
+ * re-derives before anything reads it: the tasks-to-allocate chunks of the queried jobs where their cache is invalid, and — on the engine path — the scratch
+ * tables of the domain tree (free resources, allocatable pods, ratios, keys), the order of the children inside a sibling set (every subSetNodesFn of an action
+ * sorts the sets it reads first) and the slots of the preferred-level node scores.  The scores themselves (calculateNodeScores) are NOT returned and NOT left
+ * behind for kai_best_nodes / kai_ordered_nodes: a query there is scored without a topology term.  Out of scope of this call.
+ * Two paths, the same answer.  Chip-wide (KAI_SUBSET_PATH_WIDE): a workgroup per query surveys the nodes, rolls the sums up the tree in a table of its own, ranks
+ * the siblings and lists the fitting domains; taken for the whole call when the topology plugin is loaded, the session's quantities add exactly in any order,
+ * there are no shared-GPU requests and no MIG rows, and every topology has at most 8 levels and paths that fit 63 bits ((domains + topologies)^levels).
+ * Otherwise, and with KAI_SUBSET_ENGINE_PATH, one lane calls the engine's own subset_nodes query by query (KAI_SUBSET_PATH_ENGINE).  Sibling sets that
+ * sortTreeFromRoot does not reach (outside the common domain's sub-tree, or below the preferred level where the required level lies deeper) have no order in the
+ * reference; the chip-wide path lists them by domain index, the engine path as the last action left them.
+ * Refusals, all decided before the first write to any output, leave the session open and unchanged:
+ *  - KAI_ERR_INVALID_ARG: a wrong version, unknown flag bits; a negative count or capacity; a NULL array with a count above 0, NULL params or
+ *    n_sets_out; a job, group, pod-set or nodeset out of range; a group or pod-set that is not the job's; both group and podset given;
+ *  - KAI_ERR_STATE: no open session;  KAI_ERR_UNSUPPORTED: a handle of a sharded group (n_gpus > 1).
+ * KAI_ERR_CAPACITY: the sets of all queries exceed sets_cap, known once the device has counted them; *n_sets_out holds the number needed and the other outputs
+ * are untouched.  n_queries x (domains of the largest topology + 1) always suffices.  n_queries == 0: KAI_OK without a launch, *n_sets_out = 0, path NONE. */
+#define KAI_SUBSET_VERSION 1u
+#define KAI_SUBSET_ENGINE_PATH 0x1u      /* take the engine walk even where the chip-wide path qualifies (tests, A/B) */
+#define KAI_SUBSET_PATH_NONE 0
+#define KAI_SUBSET_PATH_WIDE 1
+#define KAI_SUBSET_PATH_ENGINE 2
+#define KAI_SUBSET_PARENT (-1)           /* kai_node_set.domain: "the parent node set as it is" */
+#define KAI_SUBSET_ROOT(t) (-2 - (t))    /* the root domain of topology t: every node of the parent set that is part of t */
+enum { KAI_SUBSET_OK = 0,          /* n_sets >= 1 */
+       KAI_SUBSET_NO_TOPOLOGY = 1, /* the named topology does not exist (constraint topology -2): no set */
+       KAI_SUBSET_NO_FIT = 2,      /* the common domain, or every domain of the relevant levels, cannot take the tasks: no set */
+       KAI_SUBSET_BAD_LEVEL = 3 }; /* the function returns an error: no level given, or a level the topology does not have */
+typedef struct kai_subset_params { uint32_t version; uint32_t flags; } kai_subset_params;
+typedef struct kai_subset_query  { int32_t job; int32_t group; int32_t podset; int32_t nodeset; } kai_subset_query;
+typedef struct kai_subset_answer { int32_t status; int32_t n_sets; int32_t first; int32_t tasks; int32_t common_domain; int32_t pad; } kai_subset_answer;
+typedef struct kai_node_set      { int32_t domain; int32_t level; int32_t allocatable_pods; int32_t n_nodes; } kai_node_set;
+typedef struct kai_subset_result { int64_t n_sets; int32_t path; int32_t pad; } kai_subset_result;
+int kai_subset_nodes(kai_core* core, const kai_subset_params* params,
+                     const kai_subset_query* queries, int32_t n_queries,
+                     const uint32_t* nodeset_bitmaps, int32_t n_nodesets,      /* parent node sets: the rows and bit convention of kai_best_nodes */
+                     kai_subset_answer* answers_out /* [n_queries] */,
+                     kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out,
+                     uint32_t* bitmaps_out /* [sets_cap][ceil(N/32)] or NULL */,
+                     kai_subset_result* result /* may be NULL */);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

@@ -264,6 +264,44 @@ class KaiJobOrderResult(C.Structure):
     _fields_ = [("n_ordered", C.c_int32), ("path", C.c_int32), ("n_leaves", C.c_int32), ("pad", C.c_int32)]
 
 
+SUBSET_VERSION, SUBSET_ENGINE_PATH = 1, 0x1  # KAI_SUBSET_VERSION, KAI_SUBSET_ENGINE_PATH
+SUBSET_PATH_NONE, SUBSET_PATH_WIDE, SUBSET_PATH_ENGINE = 0, 1, 2  # kai_subset_result.path
+SUBSET_PARENT = -1  # KAI_SUBSET_PARENT: kai_node_set.domain of "the parent node set as it is"
+SUBSET_OK, SUBSET_NO_TOPOLOGY, SUBSET_NO_FIT, SUBSET_BAD_LEVEL = 0, 1, 2, 3  # kai_subset_answer.status
+SUBSET_STATUS_TEXT = {SUBSET_OK: "node sets", SUBSET_NO_TOPOLOGY: "the requested topology does not exist", SUBSET_NO_FIT: "no domain can take the tasks",
+                      SUBSET_BAD_LEVEL: "no level given, or a level the topology does not have"}
+
+
+def subset_root(t: int) -> int:
+    """KAI_SUBSET_ROOT(t): kai_node_set.domain of the root domain of topology t"""
+    return -2 - t
+
+
+class KaiSubsetParams(C.Structure):
+    """kai_subset_params (include/kai_core.h): kai_subset_nodes' flags."""
+    _fields_ = [("version", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KaiSubsetQuery(C.Structure):
+    """kai_subset_query: a job, its SubGroupSet (group) or pod-set (podset) or -1 / -1 for the root, and the parent node-set row (-1: all nodes)."""
+    _fields_ = [("job", C.c_int32), ("group", C.c_int32), ("podset", C.c_int32), ("nodeset", C.c_int32)]
+
+
+class KaiSubsetAnswer(C.Structure):
+    """kai_subset_answer: status (SUBSET_*), the number of node sets and where they start, len(tasks), the common domain."""
+    _fields_ = [("status", C.c_int32), ("n_sets", C.c_int32), ("first", C.c_int32), ("tasks", C.c_int32), ("common_domain", C.c_int32), ("pad", C.c_int32)]
+
+
+class KaiNodeSet(C.Structure):
+    """kai_node_set: one node set — its domain (or subset_root(t), or SUBSET_PARENT), level, AllocatablePods (-1: not set) and size."""
+    _fields_ = [("domain", C.c_int32), ("level", C.c_int32), ("allocatable_pods", C.c_int32), ("n_nodes", C.c_int32)]
+
+
+class KaiSubsetResult(C.Structure):
+    """kai_subset_result: the node sets of all queries and the path (SUBSET_PATH_*) that found them."""
+    _fields_ = [("n_sets", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

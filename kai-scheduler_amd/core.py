@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -130,6 +130,8 @@ def load_library(path: str = LIB_PATH):
                                             C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
     lib.kai_job_order.argtypes = [C.c_void_p, C.POINTER(abi.KaiJobOrderParams), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(abi.KaiJobOrderResult)]
+    lib.kai_subset_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiSubsetParams), C.POINTER(abi.KaiSubsetQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiSubsetAnswer),
+                                     C.POINTER(abi.KaiNodeSet), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(abi.KaiSubsetResult)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -392,6 +394,42 @@ class Session:
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         self.core._check(self.core.lib.kai_job_order(self.core.handle, C.byref(params), ip(order), J, C.byref(n), ip(pos), ip(qpos), C.byref(res)))
         return order[:n.value].copy(), pos[:J], qpos[:J], res
+
+    def subset_nodes(self, jobs, groups=None, podsets=None, nodesets=None, nodeset_of=None, engine_path: bool = False, bitmaps: bool = True):
+        """kai_subset_nodes: the topology plugin's subSetNodesFn for many jobs, sub-groups or pod-sets at the session's current state.  jobs: job indices; groups /
+        podsets: per query a SubGroupSet or a pod-set of the job (-1 / None: the job's root sub-group set; at most one of the two per query); nodesets, nodeset_of:
+        the parent node sets, as for best_nodes; engine_path: the engine walk even where the chip-wide path qualifies; bitmaps: also return the sets' nodes.
+        Returns (answers, sets, masks, result): the kai_subset_answer and kai_node_set records as structured arrays (the sets of query i are
+        sets[answers["first"][i] : answers["first"][i] + answers["n_sets"][i]], in the order the action tries them), the sets' nodes as a bool array [n_sets, N]
+        (None without bitmaps; a row can be passed as a node set of best_nodes / ordered_nodes), and the kai_subset_result."""
+        jobs = np.ascontiguousarray(jobs, dtype=np.int32).ravel()
+        M, N = len(jobs), self.snap.n_nodes
+        W = max((N + 31) // 32, 1)
+        _q, words, n_rows = self._node_queries(np.zeros(M, np.int32), nodesets, nodeset_of, None)
+        per = lambda v: np.full(M, -1, np.int32) if v is None else np.array([-1 if x is None else int(x) for x in np.asarray(v, dtype=object).ravel()], dtype=np.int32)
+        q = np.zeros(M, dtype=np.dtype([("job", "<i4"), ("group", "<i4"), ("podset", "<i4"), ("nodeset", "<i4")]))  # kai_subset_query
+        q["job"], q["group"], q["podset"], q["nodeset"] = jobs, per(groups), per(podsets), _q["nodeset"]
+        ans = np.zeros(max(M, 1), dtype=np.dtype([("status", "<i4"), ("n_sets", "<i4"), ("first", "<i4"), ("tasks", "<i4"), ("common_domain", "<i4"), ("pad", "<i4")]))  # kai_subset_answer
+        set_dt = np.dtype([("domain", "<i4"), ("level", "<i4"), ("allocatable_pods", "<i4"), ("n_nodes", "<i4")])  # kai_node_set
+        params = abi.KaiSubsetParams(abi.SUBSET_VERSION, abi.SUBSET_ENGINE_PATH if engine_path else 0)
+        n, res = C.c_int64(0), abi.KaiSubsetResult()
+        cap = max(64, 8 * M)
+        for _ in range(2):  # the capacity protocol: where the first guess is too small the call says how many there are, and the second call has room
+            sets = np.zeros(max(cap, 1), set_dt)
+            maps = np.zeros((max(cap, 1), W), np.uint32) if bitmaps else None
+            rc = self.core.lib.kai_subset_nodes(self.core.handle, C.byref(params), q.ctypes.data_as(C.POINTER(abi.KaiSubsetQuery)), M,
+                                                words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_rows else None, n_rows, ans.ctypes.data_as(C.POINTER(abi.KaiSubsetAnswer)),
+                                                sets.ctypes.data_as(C.POINTER(abi.KaiNodeSet)), cap, C.byref(n), maps.ctypes.data_as(C.POINTER(C.c_uint32)) if bitmaps else None, C.byref(res))
+            if rc != -4 or n.value <= cap:  # KAI_ERR_CAPACITY
+                break
+            cap = int(n.value)
+        self.core._check(rc)
+        total = int(n.value)
+        masks = None
+        if bitmaps:
+            bits = (maps[:total, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+            masks = bits.reshape(total, W * 32)[:, :N].astype(bool)
+        return ans[:M], sets[:total].copy(), masks, res
 
     def gpu_groups(self):
         """PodInfo.GPUGroups[0] of the active fraction pods (-1 elsewhere): kai_pod_gpu_groups."""

@@ -63,19 +63,23 @@ KAI_HD uint64_t bn_orderable(double d) {
 }
 KAI_HD bool bn_in_row(KAI_GP(const uint32_t) bits, int n) { return (bits[n >> 5] >> (n & 31)) & 1u; }
 
+// word w of a caller's node-set row in name-rank order: bit b = the caller's bit of node perm[32 w + b] (kai_subset_nodes.hpp re-indexes its parent rows with it too)
+KW_BODY uint32_t bn_reindex_word(int N, KAI_GP(const uint32_t) in, KAI_GP(const int32_t) perm, int w) {
+    uint32_t word = 0;
+    for (int b = 0; b < 32; b++) {
+        const int n = w * 32 + b;
+        if (n >= N) break;
+        const int o = perm[n];
+        word |= ((in[o >> 5] >> (o & 31)) & 1u) << b;
+    }
+    return word;
+}
+
 KW_BODY void bn_prep_body(const KaiCtx& c, const BnArgs& a) {
     const int64_t t = (int64_t)kw::bid() * kw::bdim() + kw::tid();
-    if (t < (int64_t)a.S * a.W) {  // one output word: bit b = the caller's bit of node perm[32 w + b]
+    if (t < (int64_t)a.S * a.W) {  // one output word
         const int s = (int)(t / a.W), w = (int)(t % a.W);
-        KAI_GP(const uint32_t) in = a.rows_in + (size_t)s * a.W;
-        uint32_t word = 0;
-        for (int b = 0; b < 32; b++) {
-            const int n = w * 32 + b;
-            if (n >= c.N) break;
-            const int o = a.perm[n];
-            word |= ((in[o >> 5] >> (o & 31)) & 1u) << b;
-        }
-        a.rows[(size_t)s * a.W + w] = word;
+        a.rows[(size_t)s * a.W + w] = bn_reindex_word(c.N, a.rows_in + (size_t)s * a.W, a.perm, w);
     }
     if (t < a.M) {
         const kai_node_query qi = a.queries[t];

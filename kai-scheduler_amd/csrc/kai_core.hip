@@ -450,9 +450,10 @@ int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params, int6
 
 }  // extern "C"
 
+// A launcher that can time its launches: with `prof` every launch runs between two events and is waited for, the milliseconds per kernel summed over the call and printed.
 // kai_job_order's kernels for jo_drive (kai_job_order.hpp); pin: where the head lands in the handle's staging.  KAI_JOB_ORDER_PROF: every launch between two events and waited
 // for, the milliseconds per kernel summed over the call and printed (tools/job_order_timing.py reads the line).  (A member template: outside the extern "C" block.)
-struct JoLauncher {
+struct ProfLauncher {
     kai_core* core; unsigned char* pin; bool prof = false; std::vector<std::pair<const char*, float>> spent;
     static dim3 g(int n) { return dim3((unsigned)n); }
     template <class F> void run(const char* name, F&& launch) {
@@ -462,12 +463,16 @@ struct JoLauncher {
         for (auto& e : spent) if (e.first == name) { e.second += ms; return; }
         spent.push_back({name, ms});
     }
-    void report(int path, int n) const {
+    void report(const char* what, const char* counted, int path, long long n) const {
         if (!prof) return;
-        std::fprintf(stderr, "kai job order: path %d ordered %d |", path, n);
+        std::fprintf(stderr, "%s: path %d %s %lld |", what, path, counted, n);
         for (const auto& e : spent) std::fprintf(stderr, " %s %.4f", e.first, e.second);
         std::fprintf(stderr, " ms\n");
     }
+};
+struct JoLauncher : ProfLauncher {
+    JoLauncher(kai_core* core_, unsigned char* pin_, bool prof_) : ProfLauncher{core_, pin_, prof_, {}} {}
+    void report(int path, int n) const { ProfLauncher::report("kai job order", "ordered", path, n); }
     void job_init(int n, int b, const KaiCtx& c) { run("k_job_init", [&] { hipLaunchKernelGGL(k_job_init, g(n), g(b), 0, core->stream, c); }); }
     void leaf_init(int n, int b, const KaiCtx& c) { run("k_leaf_init", [&] { hipLaunchKernelGGL(k_leaf_init, g(n), g(b), 0, core->stream, c); }); }
     void qualify(int n, int b, const KaiCtx& c, const JoArgs& a) { run("k_jo_qualify", [&] { hipLaunchKernelGGL(k_jo_qualify, g(n), g(b), 0, core->stream, c, a); }); }
@@ -546,6 +551,128 @@ int kai_job_order(kai_core* core, const kai_job_order_params* params, int32_t* o
     if (job_queue_pos_out && J) std::memcpy(job_queue_pos_out, h + L.qpos, (size_t)J * 4);
     *n_out = n;
     if (result) { result->n_ordered = n; result->path = path; result->n_leaves = n ? hd.n_leaves : 0; result->pad = 0; }
+    return KAI_OK;
+}
+
+}  // extern "C"
+
+// kai_subset_nodes' kernels for sn_count (kai_subset_nodes.hpp); pin: where the head lands in the handle's staging.  KAI_SUBSET_PROF: the per-launch times
+// (tools/subset_nodes_timing.py reads the line).
+struct SnLauncher : ProfLauncher {
+    SnLauncher(kai_core* core_, unsigned char* pin_, bool prof_) : ProfLauncher{core_, pin_, prof_, {}} {}
+    void tta(int n, int b, const KaiCtx& c, const SnArgs& a) { run("k_sn_tta", [&] { hipLaunchKernelGGL(k_sn_tta, g(n), g(b), 0, core->stream, c, a); }); }
+    void prep(int n, int b, const KaiCtx& c, const SnArgs& a) { run("k_sn_prep", [&] { hipLaunchKernelGGL(k_sn_prep, g(n), g(b), 0, core->stream, c, a); }); }
+    void wide(int n, int b, const KaiCtx& c, const SnArgs& a) { run("k_sn_wide", [&] { hipLaunchKernelGGL(k_sn_wide, g(n), g(b), 0, core->stream, c, a); }); }
+    void offsets(int n, int b, const KaiCtx& c, const SnArgs& a) { run("k_sn_offsets", [&] { hipLaunchKernelGGL(k_sn_offsets, g(n), g(b), 0, core->stream, c, a); }); }
+    void emit(int n, int b, const KaiCtx& c, const SnArgs& a) { run("k_sn_emit", [&] { hipLaunchKernelGGL(k_sn_emit, g(n), g(b), 0, core->stream, c, a); }); }
+    int engine(const KaiCtx& c, const SnArgs& a) { run("k_sn_engine", [&] { hipLaunchKernelGGL(k_sn_engine, dim3(1), dim3(64), 0, core->stream, c, a); }); return KAI_OK; }
+    int read_head(SnHead& hd, const SnArgs& a) {
+        HIP_TRY(core, hipGetLastError());
+        HIP_TRY(core, hipMemcpyAsync(pin, (const void*)a.head, sizeof(SnHead), hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+        std::memcpy(&hd, pin, sizeof(SnHead));
+        return KAI_OK;
+    }
+};
+
+extern "C" {
+
+int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_subset_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                     kai_subset_answer* answers_out, kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out, uint32_t* bitmaps_out, kai_subset_result* result) {
+    // every refusal before the first device call and before the first write to the caller's arrays
+    if (!core) return KAI_ERR_INVALID_ARG;
+    auto no = [&](int code, const char* why) { core->err = std::string("kai_subset_nodes: ") + why; return code; };
+    if (!params || !n_sets_out) return no(KAI_ERR_INVALID_ARG, "params / n_sets_out is NULL");
+    if (params->version != KAI_SUBSET_VERSION) return no(KAI_ERR_INVALID_ARG, "wrong params version");
+    if (params->flags & ~KAI_SUBSET_ENGINE_PATH) return no(KAI_ERR_INVALID_ARG, "unknown flag bits");
+    if (n_queries < 0 || n_nodesets < 0 || sets_cap < 0) return no(KAI_ERR_INVALID_ARG, "a negative count or capacity");
+    if (n_queries > 0 && (!queries || !answers_out)) return no(KAI_ERR_INVALID_ARG, "queries / answers_out is NULL");
+    if (n_nodesets > 0 && !nodeset_bitmaps) return no(KAI_ERR_INVALID_ARG, "nodeset_bitmaps is NULL");
+    if (sets_cap > 0 && !sets_out) return no(KAI_ERR_INVALID_ARG, "sets_out is NULL");
+    if (core->world > 1) return no(KAI_ERR_UNSUPPORTED, "a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    const KaiCtx& c = core->ctx;
+    const HostPrep& hp = core->prep;
+    for (int i = 0; i < n_queries; i++) {
+        const kai_subset_query& q = queries[i];
+        if (q.job < 0 || q.job >= c.J) return no(KAI_ERR_INVALID_ARG, "job index out of range");
+        if (q.group < -1 || q.podset < -1) return no(KAI_ERR_INVALID_ARG, "group / podset below -1");
+        if (q.group >= 0 && q.podset >= 0) return no(KAI_ERR_INVALID_ARG, "both group and podset given");
+        if ((q.group >= 0 || q.podset >= 0) && hp.groups_default) return no(KAI_ERR_INVALID_ARG, "a snapshot without groups has the root form only");
+        if (q.group >= hp.G || q.podset >= c.S) return no(KAI_ERR_INVALID_ARG, "group / podset out of range");
+        if (q.group >= 0 && hp.g_job[(size_t)q.group] != q.job) return no(KAI_ERR_INVALID_ARG, "the group is not the job's");
+        if (q.podset >= 0 && hp.g_job[(size_t)hp.s_group[(size_t)q.podset]] != q.job) return no(KAI_ERR_INVALID_ARG, "the pod-set is not the job's");
+        if (q.nodeset < -1 || q.nodeset >= n_nodesets) return no(KAI_ERR_INVALID_ARG, "nodeset outside -1 .. n_nodesets-1");
+    }
+    if (n_queries == 0) { *n_sets_out = 0; if (result) { result->n_sets = 0; result->path = KAI_SUBSET_PATH_NONE; result->pad = 0; } return KAI_OK; }
+    const int N = c.N, M = n_queries, S = n_nodesets, W = (N + 31) / 32, DT = c.D + c.T;
+    if (!core->sn_shape_ok) {  // the session's topologies: the most domains (its root included) and the most levels one of them has
+        std::vector<int> cnt((size_t)std::max(c.T, 1), 1);
+        for (int d = 0; d < c.D; d++) cnt[(size_t)hp.dom_topo[(size_t)d]]++;
+        core->sn_stride = 1; core->sn_levels = 0;
+        for (int t = 0; t < c.T; t++) { core->sn_stride = std::max(core->sn_stride, cnt[(size_t)t]); core->sn_levels = std::max(core->sn_levels, hp.topo_level_off[(size_t)t + 1] - hp.topo_level_off[(size_t)t]); }
+        core->sn_shape_ok = true;
+    }
+    const int stride = core->sn_stride;
+    if ((int64_t)M * stride > ((int64_t)1 << 30)) return no(KAI_ERR_CAPACITY, "n_queries x (domains of the largest topology + 1) above 2^30");
+    HIP_TRY(core, hipSetDevice(core->device));
+    const bool wide = !(params->flags & KAI_SUBSET_ENGINE_PATH) && sn_wide_session(c, core->sn_levels);
+    // workgroups of k_sn_wide: as k_bn_scan's grid, and no more than 256 MiB of domain tables
+    const int cus = device_cus(core);
+    const size_t table_bytes = (size_t)std::max(DT, 1) * (KAI_MAX_RES * 8 + 8 + 8 + 4 + 4 + 4);
+    const int wgs = wide ? (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(M, cus * KAI_SN_WGS_PER_CU), ((size_t)256 << 20) / table_bytes)) : 0;
+    const int n_children = DT > 0 ? hp.dom_child_off[(size_t)DT] : 0;
+    // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
+    const SnLayout L(N, M, S, W, stride, DT, n_children, wgs);
+    bool grew = false;
+    KAI_TRY(reserve(core, core->sn_dev, L.end, L.end + L.end / 4, &grew));
+    if (grew) core->sn_tab_ok = false;  // (the new scratch does not hold the session's tables)
+    const size_t pin_need = L.up_end + sizeof(SnHead);  // [what is sent][the head between the launches]
+    KAI_TRY(reserve(core, core->sn_pin, pin_need, std::max<size_t>(pin_need + pin_need / 4, (size_t)1 << 16)));
+    unsigned char* h = core->sn_pin.p; unsigned char* d = core->sn_dev.p;
+    // ---- one upload: [queries | rows | the zeroed head], behind the session's tables (both permutations, the children table) when the scratch does not hold them yet
+    const size_t up0 = core->sn_tab_ok ? L.queries : 0;
+    if (!core->sn_tab_ok) {
+        int32_t* rank = reinterpret_cast<int32_t*>(h + L.rank);
+        if (N > 0) std::memcpy(h + L.perm, core->perm.data(), (size_t)N * 4);
+        for (int i = 0; i < N; i++) rank[core->perm[(size_t)i]] = i;
+        if (n_children > 0) std::memcpy(h + L.children, hp.dom_children.data(), (size_t)n_children * 4);
+    }
+    std::memcpy(h + L.queries, queries, (size_t)M * sizeof(kai_subset_query));
+    if (S > 0 && W > 0) std::memcpy(h + L.rows_in, nodeset_bitmaps, (size_t)S * W * 4);
+    std::memset(h + L.head, 0, sizeof(SnHead));
+    HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, L.up_end - up0, hipMemcpyHostToDevice, core->stream));
+    core->sn_tab_ok = true;
+    SnArgs a = sn_bind_args(d, L, M, S, W, stride);
+    a.want_bitmaps = bitmaps_out ? 1 : 0;
+    KaiCtx cq = c; cq.action = KAI_ACTION_ALLOCATE;  // (the chunk the allocate action hands over)
+    // ---- the walks and the count, behind one small download
+    SnLauncher launcher(core, h + L.up_end, std::getenv("KAI_SUBSET_PROF") != nullptr);
+    SnHead hd{}; int path = KAI_SUBSET_PATH_NONE;
+    const int rcd = sn_count(launcher, cq, a, wide, KAI_SN_WG, wgs, hd, path);
+    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[160]; std::snprintf(buf, sizeof buf, "kai_subset_nodes: engine fault code %d (engine source line %d)", hd.fault, hd.fault_line); core->err = buf; return rcd; }
+    if (rcd) return rcd;
+    const int64_t total = hd.total;
+    if (total > sets_cap) { *n_sets_out = total; return no(KAI_ERR_CAPACITY, "sets_cap is below the number of node sets (*n_sets_out holds it)"); }
+    // ---- the records and the bitmap rows into a buffer of their own, then one download: [answers][sets | bitmaps]
+    const size_t set_bytes = (size_t)total * sizeof(kai_node_set), map_bytes = bitmaps_out ? (size_t)total * W * 4 : 0, ans_bytes = (size_t)M * sizeof(kai_subset_answer);
+    if (total > 0) {
+        KAI_TRY(reserve(core, core->sn_out, set_bytes + map_bytes, set_bytes + map_bytes + (set_bytes + map_bytes) / 4));
+        a.sets = (KAI_GP(kai_node_set))core->sn_out.p; a.bitmaps = (KAI_GP(uint32_t))(core->sn_out.p + set_bytes);
+        launcher.emit((int)std::min<int64_t>(total, (int64_t)cus * KAI_SN_WGS_PER_CU), KAI_SN_WG, cq, a);
+        HIP_TRY(core, hipGetLastError());
+    }
+    const size_t down = ans_bytes + set_bytes + map_bytes;
+    KAI_TRY(reserve(core, core->sn_pin, down, std::max<size_t>(down + down / 4, (size_t)1 << 16)));  // (what the staging held has been sent)
+    h = core->sn_pin.p;
+    HIP_TRY(core, hipMemcpyAsync(h, d + L.answers, ans_bytes, hipMemcpyDeviceToHost, core->stream));
+    if (total > 0) HIP_TRY(core, hipMemcpyAsync(h + ans_bytes, core->sn_out.p, set_bytes + map_bytes, hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    launcher.report("kai subset nodes", "sets", path, total);
+    std::memcpy(answers_out, h, ans_bytes);
+    if (total > 0) { std::memcpy(sets_out, h + ans_bytes, set_bytes); if (bitmaps_out) std::memcpy(bitmaps_out, h + ans_bytes + set_bytes, map_bytes); }
+    *n_sets_out = total;
+    if (result) { result->n_sets = total; result->path = path; result->pad = 0; }
     return KAI_OK;
 }
 

@@ -896,6 +896,10 @@ struct EngineBig {
     KAI_GP(const uint32_t) fbits[KAI_TDEPTH];  // node set of the DFS frame at each depth (frame_bits)
 };
 
+// what subSetNodesFn reads of its tasks (Engine::subset_tasks), and what kai_subset_nodes wants to know of a call beside the node sets (Engine::subset_nodes)
+struct SubsetTasks { double tr[KAI_MAX_RES], mx[KAI_MAX_RES]; int32_t tasks, homogeneous, one_pod_only, pad; };
+struct SubsetWhy { int32_t status, tasks, common; };
+
 template <class Backend>
 struct Engine {
     Backend& be;
@@ -1937,12 +1941,13 @@ struct Engine {
     }
     KAI_HD static double rd_floor_any(double x) { double t = (double)(int64_t)x; return t > x ? t - 1.0 : t; }
     // getJobRatioToFreeResources (plugins/topology/job_filtering.go:491-524); tr = summed request of the tasks
-    KAI_HD double job_ratio(const double* tr, int d) const {
+    KAI_HD double job_ratio(const double* tr, int d) const { return job_ratio_fr(tr, cx().dom_free + (size_t)d * KAI_MAX_RES); }
+    // ... against a domain's free resources wherever they are kept (kai_subset_nodes.hpp: a workgroup's own table)
+    KAI_HD double job_ratio_fr(const double* tr, KAI_GP(const double) fr) const {
         double dominant = 0.0;
         bool none = !(tr[KAI_RES_GPU] > 0) && !(tr[KAI_RES_CPU] > 0) && !(tr[KAI_RES_MEM] > 0);
         for (int r = KAI_RES_PODS; r < cx().R; r++) if (tr[r] > 0) none = false;   // a scalar the empty resource does not have
         if (none) return dominant;
-        KAI_GP(const double) fr = cx().dom_free + (size_t)d * KAI_MAX_RES;
         if (tr[KAI_RES_GPU] > 0) dominant = kmax(dominant, tr[KAI_RES_GPU] / fr[KAI_RES_GPU]);
         {   double tv = quantity_value_milli((double)(int64_t)tr[KAI_RES_CPU]), fv = quantity_value_milli((double)(int64_t)fr[KAI_RES_CPU]);
             if (tv != 0) dominant = kmax(dominant, fv == 0 ? 1000.0 : tv / fv); }
@@ -2022,29 +2027,57 @@ struct Engine {
         }
         return 0;
     }
-    // subSetNodesFn (plugins/topology/job_filtering.go:34-112) for a sub-group (grp = SubGroupSet, or ps = pod-set) of job j over the node set
-    // `parent`.  Writes the node sets in order to sets_out: a domain index, or -1 = "the parent set as it is".  Returns their number
-    // (0 = no node set / configuration error).  Control-lane code over the HBM domain tables.
-    KAI_HD int subset_nodes(int j, int key, int tc_topo, int tc_req, int tc_pref, int grp, int ps, const int32_t* chunk, int nt,
-                            KAI_GP(const uint32_t) parent, KAI_GP(int32_t) sets_out) {
-        const KaiCtx& c = cx();
-        if (!(c.plugins & KAI_PLUGIN_TOPOLOGY)) { sets_out[0] = -1; return 1; }
-        if (tc_topo == -2) return 0;  // "Requested topology does not exist"
-        int tasks = 0; for (int i = 0; i < nt; i++) if (task_in_subgroup(chunk[i], grp, ps)) tasks++;
-        if (tc_topo < 0 || tasks == 0) { sets_out[0] = -1; return 1; }
-        const int t = tc_topo, row0 = c.topo_level_off[t], L = c.topo_level_off[t + 1] - row0, N = c.N, DT = c.D + c.T, root = c.D + t, R = c.R;
-        // tasks: summed request, element-wise maximum, homogeneity (useRepresentorPodsAccounting :550-571)
-        double tr[KAI_MAX_RES], mx[KAI_MAX_RES]; int scalar_users[KAI_MAX_RES], gpu_users = 0;
-        for (int r = 0; r < KAI_MAX_RES; r++) { tr[r] = 0; mx[r] = 0; scalar_users[r] = 0; }
+    // the tasks of a sub-group among a chunk: summed request, element-wise maximum, homogeneity (useRepresentorPodsAccounting :550-571)
+    KAI_HD void subset_tasks(const int32_t* chunk, int nt, int grp, int ps, int tasks, SubsetTasks& o) const {
+        const int R = cx().R;
+        int scalar_users[KAI_MAX_RES], gpu_users = 0;
+        for (int r = 0; r < KAI_MAX_RES; r++) { o.tr[r] = 0; o.mx[r] = 0; scalar_users[r] = 0; }
         for (int i = 0; i < nt; i++) {
             int p = chunk[i]; if (!task_in_subgroup(p, grp, ps)) continue;
-            for (int r = 0; r < R; r++) { double v = preq(p, r); tr[r] += v; if (v > mx[r]) mx[r] = v; if (r >= KAI_RES_PODS && v != 0) scalar_users[r]++; }
+            for (int r = 0; r < R; r++) { double v = preq(p, r); o.tr[r] += v; if (v > o.mx[r]) o.mx[r] = v; if (r >= KAI_RES_PODS && v != 0) scalar_users[r]++; }
             if (preq(p, KAI_RES_GPU) > 0) gpu_users++;
         }
         bool homogeneous = !(gpu_users != tasks && gpu_users != 0);
         for (int r = KAI_RES_PODS; r < R; r++) if (scalar_users[r] != 0 && scalar_users[r] != tasks) homogeneous = false;
-        bool one_pod_only = !(mx[KAI_RES_CPU] > 0) && !(mx[KAI_RES_MEM] > 0) && !(mx[KAI_RES_GPU] > 0) && mx[KAI_RES_PODS] <= 1;
-        for (int r = KAI_RES_PODS + 1; r < R; r++) if (mx[r] > 0) one_pod_only = false;
+        bool one_pod_only = !(o.mx[KAI_RES_CPU] > 0) && !(o.mx[KAI_RES_MEM] > 0) && !(o.mx[KAI_RES_GPU] > 0) && o.mx[KAI_RES_PODS] <= 1;
+        for (int r = KAI_RES_PODS + 1; r < R; r++) if (o.mx[r] > 0) one_pod_only = false;
+        o.tasks = tasks; o.homogeneous = homogeneous ? 1 : 0; o.one_pod_only = one_pod_only ? 1 : 0; o.pad = 0;
+    }
+    // hasActiveAllocatedTasks && a required level (:321-347): only sub-trees that already hold an active pod of these pod-sets are relevant
+    KAI_HD bool subset_restrict_active(int j, int tc_req, int grp, int ps) const {
+        const KaiCtx& c = cx();
+        if (tc_req < 0) return false;
+        for (int k = 0; k < c.j_n_ps[j]; k++) { int s2 = c.j_first_ps[j] + k; if ((ps >= 0 ? s2 == ps : podset_in_group(s2, grp)) && ps_act(s2) > 0) return true; }
+        return false;
+    }
+    // does the sub-tree of `anc` (a domain of level tc_req in the rows from row0 on) hold an active allocated pod of the sub-group?
+    KAI_HD bool subset_has_active(int j, int row0, int tc_req, int anc, int grp, int ps) const {
+        const KaiCtx& c = cx();
+        for (int i = 0; i < c.j_n_pods[j]; i++) {
+            int p = c.j_first_pod[j] + i;
+            if (!st_active_allocated(c.p_status[p]) || c.p_node[p] < 0 || !task_in_subgroup(p, grp, ps)) continue;
+            if (node_dom(row0 + tc_req, c.p_node[p]) == anc) return true;
+        }
+        return false;
+    }
+    // subSetNodesFn (plugins/topology/job_filtering.go:34-112) for a sub-group (grp = SubGroupSet, or ps = pod-set) of job j over the node set
+    // `parent`.  Writes the node sets in order to sets_out: a domain index, or -1 = "the parent set as it is".  Returns their number
+    // (0 = no node set / configuration error).  Control-lane code over the HBM domain tables.
+    KAI_HD int subset_nodes(int j, int key, int tc_topo, int tc_req, int tc_pref, int grp, int ps, const int32_t* chunk, int nt,
+                            KAI_GP(const uint32_t) parent, KAI_GP(int32_t) sets_out, SubsetWhy* why = nullptr) {
+        const KaiCtx& c = cx();
+        // `why` (kai_subset_nodes): which of the outcomes that return 0 it was, the number of tasks and the common domain (-1 = the function returned before it)
+        auto say = [&](int status, int n_tasks, int common) { if (why) { why->status = status; why->tasks = n_tasks; why->common = common; } };
+        say(KAI_SUBSET_OK, 0, -1);
+        if (!(c.plugins & KAI_PLUGIN_TOPOLOGY)) { int n = 0; for (int i = 0; i < nt; i++) if (task_in_subgroup(chunk[i], grp, ps)) n++; say(KAI_SUBSET_OK, n, -1); sets_out[0] = -1; return 1; }
+        int tasks = 0; for (int i = 0; i < nt; i++) if (task_in_subgroup(chunk[i], grp, ps)) tasks++;
+        if (tc_topo == -2) { say(KAI_SUBSET_NO_TOPOLOGY, tasks, -1); return 0; }  // "Requested topology does not exist"
+        say(KAI_SUBSET_OK, tasks, -1);
+        if (tc_topo < 0 || tasks == 0) { sets_out[0] = -1; return 1; }
+        const int t = tc_topo, row0 = c.topo_level_off[t], L = c.topo_level_off[t + 1] - row0, N = c.N, DT = c.D + c.T, root = c.D + t, R = c.R;
+        SubsetTasks sum; subset_tasks(chunk, nt, grp, ps, tasks, sum);
+        const double* tr = sum.tr; const double* mx = sum.mx;
+        const bool homogeneous = sum.homogeneous != 0, one_pod_only = sum.one_pod_only != 0;
         // lowestCommonDomainID (common.go:17-67) over the nodes of `parent` that are part of the topology
         int domain = root, dl = -1;
         KAI_TCLK0
@@ -2140,6 +2173,7 @@ struct Engine {
         }
         ts.domain = domain; ts.dl = dl;
         KAI_TCLK(23)
+        say(KAI_SUBSET_NO_FIT, tasks, domain);
         if (!domain_fits(domain, tr, tasks)) return 0;
         // sortTreeFromRoot :447-486: children by ratio descending, then by domain ID, down to the preferred (else required) level
         const int max_depth = tc_pref >= 0 ? tc_pref : tc_req;
@@ -2189,12 +2223,11 @@ struct Engine {
         }
         KAI_TCLK(25)
         // getJobAllocatableDomains :265-310 over calculateRelevantDomainLevels :381-425 (from the preferred level up to the required one)
+        say(KAI_SUBSET_BAD_LEVEL, tasks, domain);
         if (tc_req < 0 && tc_pref < 0) return 0;
         if (tc_req >= L || tc_pref >= L) return 0;  // a level the topology does not have
-        bool restrict_active = false;
-        if (tc_req >= 0) {  // hasActiveAllocatedTasks && required level: only sub-trees that already hold an active pod of these pod-sets (:321-347)
-            for (int k = 0; k < c.j_n_ps[j]; k++) { int s2 = c.j_first_ps[j] + k; if ((ps >= 0 ? s2 == ps : podset_in_group(s2, grp)) && ps_act(s2) > 0) restrict_active = true; }
-        }
+        say(KAI_SUBSET_NO_FIT, tasks, domain);
+        const bool restrict_active = subset_restrict_active(j, tc_req, grp, ps);
         KAI_GP(int32_t) chosen = c.dom_tmp + DT;      // 1 = allocatable domain of a relevant level
         int n_chosen = 0;
         bool found_pref = false, found_req = false;
@@ -2213,13 +2246,7 @@ struct Engine {
                 if (c.dom_topo[d] != t || c.dom_level[d] != l) continue;
                 if (restrict_active) {
                     int anc = d; while (anc >= 0 && c.dom_level[anc] > tc_req) anc = c.dom_parent[anc];
-                    bool has = false;
-                    if (anc >= 0 && c.dom_level[anc] == tc_req) for (int i = 0; i < c.j_n_pods[j] && !has; i++) {
-                        int p = c.j_first_pod[j] + i;
-                        if (!st_active_allocated(c.p_status[p]) || c.p_node[p] < 0 || !task_in_subgroup(p, grp, ps)) continue;
-                        if (node_dom(row0 + tc_req, c.p_node[p]) == anc) has = true;
-                    }
-                    if (!has) continue;
+                    if (!(anc >= 0 && c.dom_level[anc] == tc_req && subset_has_active(j, row0, tc_req, anc, grp, ps))) continue;
                 }
                 if (domain_fits(d, tr, tasks)) { chosen[d] = 1; n_chosen++; }
             }
@@ -2236,6 +2263,7 @@ struct Engine {
                 ts.op = 13; be.topo_scan(c, ts);
                 ts.op = 14; ts.out = (KAI_GP(uint32_t))sets_out; be.topo_scan(c, ts);
                 KAI_TCLK(27)
+                say(KAI_SUBSET_OK, tasks, domain);
                 return n_chosen;
             }
         }
@@ -2254,6 +2282,7 @@ struct Engine {
             for (int i = b; i < e; i++) if (chosen[ord[i]]) sets_out[n_sets++] = ord[i];
         }
         KAI_TCLK(27)
+        say(n_sets ? KAI_SUBSET_OK : KAI_SUBSET_NO_FIT, tasks, domain);
         return n_sets;
     }
     // node set of a frame: parent ∩ nodes of the topology ∩ nodes of domain d   (d = -1: the parent set itself)

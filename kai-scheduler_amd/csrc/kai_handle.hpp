@@ -27,6 +27,7 @@
 #include "kai_ops_apply.hpp"
 #include "kai_stale_gangs.hpp"
 #include "kai_job_order.hpp"
+#include "kai_subset_nodes.hpp"
 
 using namespace kai;
 
@@ -111,7 +112,10 @@ struct kai_core {
     HandleBuf sg_pin{true}, sg_dev{false}; size_t sg_job_cap = 0, sg_wg_cap = 0;
     // kai_job_order (kai_job_order.hpp): pinned staging and device scratch (the call's outputs, the tree tables, the plan's pools), grow, live with the handle
     HandleBuf jo_pin{true}, jo_dev{false};
-    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
+    // kai_subset_nodes (kai_subset_nodes.hpp): pinned staging, device scratch and the emitted sets' own buffer, grow, live with the handle; whether the scratch holds this session's
+    // tables (both node permutations, the open's children table); the session's topologies: raw records a query can have, the most levels of one (found with the first call)
+    HandleBuf sn_pin{true}, sn_dev{false}, sn_out{false}; bool sn_tab_ok = false, sn_shape_ok = false; int sn_stride = 1, sn_levels = 0;
+    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &sn_pin, &sn_dev, &sn_out, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
 };
 
 // leave the function with a step's status unless it is KAI_OK; a HIP call's error becomes KAI_ERR_HIP with the call's text in kai_last_error

@@ -22,6 +22,7 @@ import "C"
 
 import (
 	"fmt"
+	mathbits "math/bits"
 	"sort"
 	"time"
 	"unsafe"
@@ -1010,6 +1011,74 @@ func JobOrder() *reflectjoborder.ReflectJobOrder {
 		doc.QueueOrder[job.Queue] = append(doc.QueueOrder[job.Queue], jo) // pop order filtered by the leaf queue: what job_queue_pos_out indexes
 	}
 	return doc
+}
+
+// SubsetNodes: the SubsetNodesFn of the default tier — the topology plugin's subSetNodesFn (plugins/topology/job_filtering.go:34-112) — for the root sub-group
+// sets of many jobs over all nodes, decided by the device against ITS session state in ONE kai_subset_nodes call (two where the first guess of the capacity is too
+// small: the call then says how many sets there are).  sets[i] are the node sets of jobs[i] in the order the allocate action tries them, as BestNodes /
+// OrderedNodes take them for nodeSets; no set: the job cannot be placed under its constraint now (status[i] says why: C.KAI_SUBSET_NO_TOPOLOGY, _NO_FIT,
+// _BAD_LEVEL).  The composed walk of a topology gang whose pods only Go can filter (KAI_POD_CPU_FALLBACK): SubsetNodes, then per node set OrderedNodes for the
+// gang's tasks and the Go filter down each list — no pass over the nodes on the host.  The call changes nothing on the device; the preferred-level node scores
+// are not part of the answer.  Inner sub-groups and pod-sets are asked through the C call with a node set's row as the parent row.  Not registered anywhere.
+// ok = false: no device session (or `fallback` already set), a job the snapshot does not know, or a refusal of the entry point: the caller asks the Go session.
+func SubsetNodes(jobs []*podgroup_info.PodGroupInfo) (sets [][][]*node_info.NodeInfo, status []int, ok bool) {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return nil, nil, false
+	}
+	pack := current.pack
+	if len(jobs) == 0 {
+		return nil, nil, true
+	}
+	jobOf := make(map[*podgroup_info.PodGroupInfo]int, len(pack.jobs))
+	for i, j := range pack.jobs {
+		jobOf[j] = i
+	}
+	queries := make([]C.kai_subset_query, len(jobs))
+	for i, j := range jobs {
+		idx, known := jobOf[j]
+		if !known {
+			return nil, nil, false
+		}
+		queries[i] = C.kai_subset_query{job: C.int32_t(idx), group: -1, podset: -1, nodeset: -1}
+	}
+	words := (len(pack.nodes) + 31) / 32
+	params := C.kai_subset_params{version: C.KAI_SUBSET_VERSION}
+	answers := make([]C.kai_subset_answer, len(jobs))
+	capSets := 8*len(jobs) + 64
+	var records []C.kai_node_set
+	var rows []C.uint32_t
+	var n C.int64_t
+	for try := 0; ; try++ {
+		records = make([]C.kai_node_set, capSets+1)
+		rows = make([]C.uint32_t, capSets*words+1)
+		// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+		rc := C.kai_subset_nodes(core, &params, &queries[0], C.int32_t(len(queries)), nil, 0, &answers[0], &records[0], C.int64_t(capSets), &n, &rows[0], nil)
+		if rc == C.KAI_ERR_CAPACITY && try == 0 {
+			capSets = int(n) // decided before the first write: the arrays are as they were
+			continue
+		}
+		if rc != 0 {
+			return nil, nil, false
+		}
+		break
+	}
+	sets = make([][][]*node_info.NodeInfo, len(jobs))
+	status = make([]int, len(jobs))
+	for i, a := range answers {
+		status[i] = int(a.status)
+		sets[i] = make([][]*node_info.NodeInfo, int(a.n_sets))
+		for k := 0; k < int(a.n_sets); k++ {
+			r := int(a.first) + k
+			set := make([]*node_info.NodeInfo, 0, int(records[r].n_nodes))
+			for w := 0; w < words; w++ {
+				for bits := uint32(rows[r*words+w]); bits != 0; bits &= bits - 1 {
+					set = append(set, pack.nodes[w*32+mathbits.TrailingZeros32(bits)])
+				}
+			}
+			sets[i][k] = set
+		}
+	}
+	return sets, status, true
 }
 
 // replay: the committed operations through the real Statement.  kai_op.stmt numbers the Statements of the action in
