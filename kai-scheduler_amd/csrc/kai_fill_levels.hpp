@@ -33,6 +33,8 @@
 // emulator runs this kernel's wavefronts as fibers that really interleave (KW_EMU_ORDER), tests/host_sim shadows every launch with the scalar C++ fill.  Clusters with more than
 // eight levels (16-device nodes) or with static class bitmaps stay on k_fill_counts / k_fill_buckets.
 #pragma once
+#include <type_traits>
+
 #include "kai_fill_counts.hpp"
 
 namespace kai {
@@ -44,8 +46,12 @@ constexpr int KFL_SHORT = 16;                              // a gang of one clas
 constexpr int KFL_JOB_SHIFT = 23;                          // a command's bits 23-28: its job's index within the stretch (or-ed in by the counting machine: kfl_cmd knows nothing of it)
 constexpr int KFL_PAIRS = KFL_LMAX * (KFL_LMAX - 1) / 2;   // (source level g, target level g2 < g)
 // -DKFL_PROF, a worker's clocks per kind of event: 0 one node leaves, its word stays | 1 one node, the word is emptied | 2 several nodes of one word | 3 several nodes over more than
-// one word | 4 nodes arrive in the cached word | 5 in an empty word | 6 in another non-empty word
-constexpr int KFL_WKINDS = 7;
+// one word | 4 nodes arrive in the cached word | 5 in an empty word | 6 in another non-empty word | 7 a RUN of insertions taken in lanes (events: runs) | 8 the entries of those
+// runs (events: entries; no cycles of their own) | 9 a run sent the serial way because its source was behind (cycles: the look that found it out)
+constexpr int KFL_WKINDS = 10;
+#ifndef KFL_RUN_MIN
+#define KFL_RUN_MIN 2                                      // insertions in front of the next removal that make a run (DESIGN.md 5.2d "Runs of insertions": the replay has a run of two at less than two single insertions)
+#endif
 // a command, 8 bytes: bits 0-3 g, 4-7 g2, 8-11 per, 12-22 k | the upper word: tbase — the first k nodes of level g take `per` tasks each and move to level g2 (0: no level); their tasks are t_node[tbase ..)
 // A word with g = 0 is no command but a stretch's MARKER: the counting machine writes one in front of every stretch's commands.
 KW_BODY uint64_t kfl_cmd(int g, int g2, int k, int per, int tbase) { return (uint64_t)((uint32_t)g | ((uint32_t)g2 << 4) | ((uint32_t)per << 8) | ((uint32_t)k << 12)) | ((uint64_t)(uint32_t)tbase << 32); }
@@ -127,6 +133,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
     }
     kw::sync();
     const int V = rp.mode != 1 ? b.q_valid[c.Q] : 0;  // mode 1: dead classes only (before the first plan)
+    int64_t my_runs = 0;  // -DKFL_RUN_STATS (tests/test_fill_levels_insert_runs.py builds the emulated replay with it; the product carries none of it): a worker's runs of insertions, taken in lanes | sent the serial way << 32, summed into FillStatus.rescans3 at the end
     const int wave = kw::uni(tid >> 6);  // (the compiler takes anything computed from the thread's number for different in every lane: told otherwise, a wavefront's role, its level and its tests sit on the scalar unit)
     if (wave == 0) {
         // ------------------------------------------------------------------ wavefront 0: the counting machine.
@@ -402,7 +409,14 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         }
     } else if (wave <= v.LV) {
         // ------------------------------------------------------------------ wavefront G = 1 .. LV: the worker of level G.  Everything here is uniform over the wavefront.
-        const int G = wave, lw = (G - 1) * v.NW, l1 = (G - 1) * v.NW1;
+        // Under bin-pack the body exists twice: LOW is wavefront 1's, the lowest level's.  Its nodes leave for no level (g2 < g = 1), so its removals form no hand-over entry,
+        // look at no pair counter and store nothing for one — a compile-time fact there.  (Under spread the lowest level is a source only when it is the highest non-empty
+        // one, and no run of insertions finds its source ahead — a spread command brings a node per word it spans, the targets wait for the sources: DESIGN.md 5.2d — so the
+        // spread instantiation keeps ONE body, without runs.)
+        constexpr bool RUNS = !SP && KFL_RUN_MIN <= 64;
+        auto worker = [&](auto low_) {
+        constexpr bool LOW = decltype(low_)::value;
+        const int G = LOW ? 1 : wave, lw = (G - 1) * v.NW, l1 = (G - 1) * v.NW1;
         KW_LDS_PTR(uint64_t) dm = (KW_LDS_PTR(uint64_t))&L.dummy[0];
         // the level's first summary in registers: lane j holds the word of group j (bit i: word 64 j + i holds a node; NW1 <= 64).  Only this worker reads and writes it and nobody
         // wants it back, so after this load the s1 region of the LDS is not touched again: "the word is empty now" and "the word was empty" are lane writes.
@@ -415,6 +429,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         // lane t: this worker's hand-over ring to level t + 1 — entries written, the consumer's progress as last read; lane s: its ring from level s + 1 — entries taken
         int xp = 0, xseen = 0, xc = 0;
         int tail = 0; int64_t w_idle = 0; const int64_t w_start = kw::clock();
+        int n_runs = 0, n_serial = 0;  // runs of insertions taken in lanes / sent the serial way
 #ifdef KFL_PROF
         // the clocks per kind of event (tools/micro/fill_bench.hip -DKFL_PROF): cycles and events, kept by lane 0 in the LDS; the product build carries none of it
         int64_t wt = kw::clock();
@@ -436,6 +451,10 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                 const int nb = head - tail < 64 ? head - tail : 64;
                 const uint64_t mc = L.ring[(tail + lane) & (KFL_RING - 1)];  // (lanes beyond the batch read a slot that is not used)
                 uint64_t mine = kw::ballot(lane < nb && ((int)(mc & 15) == G || (int)((mc >> 4) & 15) == G));
+                // runb: the insertions of `mine` whose predecessor in `mine` is an insertion too — the carry of (its insertions << 1) through the commands that are not this
+                // level's lands on the next one that is.  (The top level takes nothing in: the word stays 0 there.)
+                uint64_t runb = 0;
+                if (RUNS) { const uint64_t tg = kw::ballot(lane < nb && (int)((mc >> 4) & 15) == G); runb = (~mine + (tg << 1)) & mine & tg; }
                 while (mine) {
                     KFL_WT0();
                     const int ci = __builtin_ctzll(mine); mine &= mine - 1;
@@ -446,6 +465,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                         const int per = (ca >> 8) & 15; int left = (ca >> 12) & 0x7ff, tb = kw::bcast((int)(uint32_t)(mc >> 32), ci);
                         const int pr = g2 >= 1 ? kfl_pair(G, g2) : KFL_PAIRS;  // (no level: the ring nobody reads)
                         const int xl = (g2 - 1) & 63;                          // (no level: lane 63, which is never counted up)
+                        const bool hand = !LOW && (SP || g2 >= 1);  // (the lowest level hands nothing over.  The other levels branch round the entry of a node that leaves for no level — one uniform branch against fifteen instructions and three stores: the replay has it 50 cycles a removal cheaper under bin-pack; under spread, where few nodes leave for no level, the ring nobody reads is cheaper)
 #ifdef KFL_PROF
                         const int k_all = left; int n_words = 0, n_emptied = 0;
 #endif
@@ -455,12 +475,14 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                             const int w = cw; const uint64_t mask = curw & (0 - curw), neww = curw ^ mask;
                             b.t_node[tb + (lane < per ? lane : per - 1)] = firstn;  // (its tasks all sit on it, per <= 8; the lanes beyond them store the last one's again: no branch)
                             kfl_write(&v.gw[lw + w], neww, dm);
-                            const int n_w = kw::bcast(xp, xl);
-                            if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
-                            KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
-                            e->mask = mask; e->w = w | (1 << 30);
-                            kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
-                            xp += lane == g2 - 1 ? 1 : 0;
+                            if (hand) {
+                                const int n_w = kw::bcast(xp, xl);
+                                if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
+                                KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
+                                e->mask = mask; e->w = w | (1 << 30);
+                                kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
+                                xp += lane == g2 - 1 ? 1 : 0;
+                            }
                             if (__builtin_expect(neww != 0, 1)) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
                             else {
                                 const int w1 = w >> 6; const uint64_t m1 = kw::bcast(s1v, w1) & ~(1ull << (w & 63));
@@ -496,12 +518,14 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                             kfl_write(&v.gw[lw + w], neww, dm);
                             left -= m; tb += m * per;
                             // one entry for the target level's worker
-                            const int n_w = kw::bcast(xp, xl);
-                            if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
-                            KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
-                            e->mask = mask; e->w = w | (left == 0 ? 1 << 30 : 0);
-                            kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
-                            xp += lane == g2 - 1 ? 1 : 0;
+                            if (hand) {
+                                const int n_w = kw::bcast(xp, xl);
+                                if (__builtin_expect(n_w - kw::bcast(xseen, xl) >= KFL_XR, 0)) { int t; while (n_w - (t = kfl_load(&L.xtail[pr])) >= KFL_XR) kw::relax(); if (lane == xl) xseen = t; }
+                                KW_LDS_PTR(FlMove) e = lane == 0 ? (KW_LDS_PTR(FlMove))&L.x[pr][n_w & (KFL_XR - 1)] : (KW_LDS_PTR(FlMove))&L.xdummy[lane];
+                                e->mask = mask; e->w = w | (left == 0 ? 1 << 30 : 0);
+                                kw::lds_store_ordered((int32_t*)&e->seq, n_w + 1);
+                                xp += lane == g2 - 1 ? 1 : 0;
+                            }
                             if (__builtin_expect(neww != 0, 1)) { curw = neww; firstn = (w << 6) + __builtin_ctzll(neww); }
                             else {  // the word is empty: its bit in the first summary goes (a lane write), and the level's first node is the first node of the next word
                                 const int w1 = w >> 6; const uint64_t m1 = kw::bcast(s1v, w1) & ~(1ull << (w & 63));
@@ -522,6 +546,61 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                     } else {
                         // TARGET: take the command's nodes in as the source level's worker hands them over
                         const int pr = kfl_pair(g, G);
+                        if (RUNS && (runb & mine & (0 - mine)) != 0) {
+                            // A RUN OF INSERTIONS: the next command of `mine` brings nodes too.  Between two removals insertions commute — they or bits into words, set summary
+                            // bits and lower the first node —, so the insertions from this command's source level in front of the next other command of `mine` (a removal, or an
+                            // insertion from another level: that one starts a run of its own), KFL_RUN_MIN or more of them and at most 16 command slots on, are taken in ONE pass:
+                            // lane i reads the i-th entry of the pair's ring behind the ones taken (the ring is KFL_XR = 32 entries: lanes 32-63 read what lanes 0-31 read and take
+                            // no part), every entry lane ors its mask into its word, a uniform loop of a few scalar instructions per entry tells the first summary and finds the
+                            // first node, the ring moves on once.  Nothing here waits: if the source has not yet handed over all the run needs, nothing has been consumed and
+                            // the run goes entry by entry, which waits as it always did.
+                            const uint64_t stop = mine & ~runb;
+                            uint64_t run = mine & (stop ? (stop & (0 - stop)) - 1 : ~0ull) & (0xffffull << ci);
+                            const uint64_t other = kw::ballot((int)(mc & 15) != g) & run;
+                            run &= other ? (other & (0 - other)) - 1 : ~0ull;
+                            const int cA = 1 + __builtin_popcountll(run);  // commands of the run
+                            if (cA >= KFL_RUN_MIN) {
+                                const int nr = kw::bcast(xc, g - 1), en = nr + (lane & (KFL_XR - 1)), sl = en & (KFL_XR - 1);
+                                // sequence number first, the entry behind it in the same trip
+                                const int sq = kw::lds_load_ordered(&L.x[pr][sl].seq), wf_v = kw::lds_load_relaxed(&L.x[pr][sl].w); const uint64_t mk_v = kw::lds_load_relaxed(&L.x[pr][sl].mask);
+                                const uint32_t vm = (uint32_t)kw::ballot(sq == en + 1), lm = (uint32_t)kw::ballot(sq == en + 1 && ((wf_v >> 30) & 1) != 0);
+                                // the run's entries: the valid prefix of the ring up to the cA-th `last` flag (a command of several entries needs no special case); 0: not all there
+                                int n = 0;
+                                const uint32_t all = (uint32_t)((1ull << cA) - 1);
+                                if (__builtin_expect((lm & all) == all, 1)) n = cA;  // (the usual run: every command brought one entry)
+                                else {
+                                    uint32_t m = lm & (uint32_t)((1ull << __builtin_ctzll(~(uint64_t)vm)) - 1);
+                                    if (__builtin_popcount(m) >= cA) { for (int j = 1; j < cA; j++) m &= m - 1; n = __builtin_ctz(m) + 1; }
+                                }
+                                if (__builtin_expect(n != 0, 1)) {
+                                    mine &= ~run; n_runs++;
+                                    {   // the masks into their words: an LDS `or` that returns nothing; lanes without an entry or into their dummy slot, two entries of one word are the LDS's business
+                                        KW_LDS_PTR(uint64_t) q = lane < n ? (KW_LDS_PTR(uint64_t))&v.gw[lw + (wf_v & 0x3fffffff)] : dm + lane;
+                                        kw::lds_or(q, mk_v);
+                                    }
+                                    // the ring moves on, behind the reads, once: a producer that waits for room is released now
+                                    kw::lds_store_ordered(&L.xtail[pr], nr + n);
+                                    xc += lane == g - 1 ? n : 0;
+                                    // entry by entry on the scalar unit: the word's bit in the first summary; the level's first node = the lowest of today's and the entries' — its word
+                                    // is the cached one, which takes the run's masks for it, or lies below it and was empty before the run (a non-empty word other than the cached one
+                                    // lies above it: tests/test_fill_levels_workers.py — for the run as a whole), so its value is the or of the run's masks for it
+                                    int minw = cw >= 0 ? cw : 0x7fffffff; uint64_t acc = curw;
+                                    for (int el = 0; el < n; el++) {
+                                        const int w = kw::bcast(wf_v, el) & 0x3fffffff, w1 = w >> 6; const uint64_t mask = kw::bcast(mk_v, el);
+                                        s1v = kw::writelane(s1v, kw::bcast(s1v, w1) | (1ull << (w & 63)), w1);
+                                        acc = w < minw ? mask : w == minw ? acc | mask : acc; minw = w < minw ? w : minw;
+                                    }
+                                    s2 = kw::ballot(s1v != 0);
+                                    cw = minw; curw = acc; firstn = (cw << 6) + __builtin_ctzll(curw);
+#ifdef KFL_PROF
+                                    { const int64_t n_ = kw::clock(); if (lane == 0) { L.wk_cyc[G - 1][7] += n_ - wt; L.wk_cnt[G - 1][7]++; L.wk_cnt[G - 1][8] += n; } wt = n_; }
+#endif
+                                    continue;
+                                }
+                                runb &= ~run; n_serial++;  // the source is behind: this command and the run's others one by one
+                                KFL_WK(9);
+                            }
+                        }
                         for (bool last = false; !last;) {
                             const int n_r = kw::bcast(xc, g - 1);
                             const int sl = n_r & (KFL_XR - 1);
@@ -561,6 +640,11 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         #undef KFL_WT0
         #undef KFL_WK
         if (lane == 0) { L.w_idle[G - 1] = w_idle; L.w_total[G - 1] = kw::clock() - w_start; }
+#ifdef KFL_RUN_STATS
+        my_runs = (int64_t)n_runs | ((int64_t)n_serial << 32);
+#endif
+        };
+        if constexpr (!SP) { if (wave == 1) worker(std::true_type{}); else worker(std::false_type{}); } else worker(std::false_type{});
     } else if (wave == v.LV + 1) {
         // ------------------------------------------------------------------ wavefront LV + 1: the bookkeeper.  It replays the commands on the capacities (lane q − 1: capq) and books,
         // for every dead-for-good gang, the capacity of its request size at its turn.  A command names its job (bits 23-28); a marker (g = 0) stands in front of every stretch's commands.
@@ -616,6 +700,9 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         if (lane == 0) { L.b_dec = total; L.w_idle[KFL_LMAX] = w_idle; L.w_total[KFL_LMAX] = kw::clock() - w_start; }
     }
     kw::sync();
+#ifdef KFL_RUN_STATS
+    if (lane == 0 && my_runs != 0) kw::atomic_add((unsigned long long*)&b.fs[0].rescans3, (unsigned long long)my_runs);  // (the counting machine wrote 0 in front of the barrier)
+#endif
     if (tid == 0) {
         b.fs[0].decisions += L.b_dec;
 #if defined(KFL_PROF) && defined(__HIPCC__)

@@ -98,7 +98,8 @@ int main(int argc, char** argv) {
 #ifdef KFL_PROF
         if (kern == 0) {  // the set workers' clocks of the last repetition: cycles / events per kind, then idle and total
             int64_t wk[KFL_LMAX][KFL_WKINDS + 1][2]; CK(hipMemcpyFromSymbol(wk, HIP_SYMBOL(kfl_prof_workers), sizeof wk));
-            const char* kinds[KFL_WKINDS] = {"one node, word stays", "one node, word emptied", "several nodes, one word", "several nodes, more words", "into the cached word", "into an empty word", "into another non-empty word"};
+            const char* kinds[KFL_WKINDS] = {"one node, word stays", "one node, word emptied", "several nodes, one word", "several nodes, more words", "into the cached word", "into an empty word", "into another non-empty word",
+                                               "a run of insertions in lanes", "entries of those runs (events only)", "a run sent the serial way: the look"};
             for (int l = 0; l < LV; l++) {
                 std::printf("  worker of level %d: idle %lld of %lld cycles |", l + 1, (long long)wk[l][KFL_WKINDS][0], (long long)wk[l][KFL_WKINDS][1]);
                 for (int k = 0; k < KFL_WKINDS; k++) std::printf(" %s: %lld cycles / %lld events (%lld each) |", kinds[k], (long long)wk[l][k][0], (long long)wk[l][k][1], (long long)(wk[l][k][1] ? wk[l][k][0] / wk[l][k][1] : 0));
