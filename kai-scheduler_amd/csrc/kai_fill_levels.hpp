@@ -42,7 +42,8 @@ namespace kai {
 constexpr int KFL_LMAX = 8;                                // levels = worker wavefronts
 constexpr int KFL_RING = 4096;                             // commands the ring holds (a gang, <= KB_PLACED_MAX commands, is written in full before it is published)
 constexpr int KFL_XR = 32;                                 // entries of a hand-over ring
-constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": it is walked in a run (its first two commands held in lanes; a third step sends it the long way)
+constexpr int KFL_SHORT = 16;                              // a gang of one class with at most this many tasks is "short": it is walked in a run (up to KFL_HELD commands of it held in lanes; one step more sends it the long way)
+constexpr int KFL_HELD = 3;                                // commands of a short gang a run holds in lanes under bin-pack (c0 .. c2).  Config 5 at full size, the big round: of 42 742 walked gangs 1 944 take three steps, 38 four, none five (DESIGN.md 5.2d "Steps in lanes"); under spread a third step does not occur there and the run holds two
 constexpr int KFL_JOB_SHIFT = 23;                          // a command's bits 23-28: its job's index within the stretch (or-ed in by the counting machine: kfl_cmd knows nothing of it)
 constexpr int KFL_PAIRS = KFL_LMAX * (KFL_LMAX - 1) / 2;   // (source level g, target level g2 < g)
 // -DKFL_PROF, a worker's clocks per kind of event: 0 one node leaves, its word stays | 1 one node, the word is emptied | 2 several nodes of one word | 3 several nodes over more than
@@ -196,6 +197,9 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         // a command's lower word without its job's index, held in lane jj of a register until the run is flushed (a gang that fails holds whatever: it is never stored)
         #define KFL_LOW(g_, g2_, k_, per_) (int)((uint32_t)(g_) | ((uint32_t)(g2_) << 4) | ((uint32_t)(per_) << 8) | ((uint32_t)(k_) << 12))
         #define KFL_HOLD1(g_, g2_, k_, per_) c1 = kw::writelane(c1, KFL_LOW(g_, g2_, k_, per_), jj)
+        #define KFL_HOLD2(g_, g2_, k_, per_) c2 = kw::writelane(c2, KFL_LOW(g_, g2_, k_, per_), jj)
+        constexpr int HELD = SP ? 2 : KFL_HELD;  // (statically unrolled below: there is no indexed register access)
+        static_assert(KFL_HELD == 3, "c0 .. c2: one more held command is one more register, one more step and one more store below");
         // THE DECISION TABLE: lane j holds the first step of job j under the mask nz_tab, as one word — all that the step is but the level's population: bits 0-11 the command's
         // lower word as it stands (g, g2, per; g = 0: no level >= q holds a node), bits 23-27 kq = the nodes the gang wants of the level (at least 1; the command's k = min(kq,
         // nodes of the level) goes to bits 12-22, which the word leaves empty), bit 28: kq nodes are NOT all of the gang (so bits 23-28 as one number equal k iff one step places
@@ -261,17 +265,19 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
             // A run stores nothing: the lower word of a gang's command goes into lane jj of c0, that of a second step into c1, and the run is FLUSHED at its end — every lane forms
             // the upper words and the job bits of its own gang's commands, a prefix sum gives it their place in the ring, head is published once.  The ring receives the words in
             // the jobs' order, as if every gang had written its own.  A first step that finds no level moves nothing (k = 0), so only a gang that takes a second step needs the
-            // state in front of it: rebuilt there from the first step's values.  A short gang that needs a third step leaves the run and goes the long way from the start.)
+            // state in front of it: rebuilt there from the first step's values, once, whatever the number of steps behind it.  Under bin-pack a third step goes into c2 the same
+            // way (KFL_HELD = 3; lane jj of nx counts the commands beyond the second) and the flush stores a lane's commands one behind the other; a short gang that needs one
+            // step more than the lanes hold leaves the run and goes the long way from the start.)
             while (todo) {
                 const uint64_t lm = todo & longm;
                 const uint64_t below = lm ? (lm & (0 - lm)) - 1 : ~0ull;  // the jobs in front of the next long one
                 uint64_t hot = todo & below;
                 todo &= ~below;
                 if (hot) {
-                    const uint64_t run0 = hot; uint64_t twor = 0, rest = 0, fail2 = 0, held;  // the run's jobs / the ones among them that committed with two commands / the ones a third step left unwalked / the ones a second step rolled back / the ones behind the first job the table says ends differently from its prediction
+                    const uint64_t run0 = hot; uint64_t twor = 0, rest = 0, fail2 = 0, held;  // the run's jobs / the ones among them that committed with two or more commands / the ones a step beyond the held ones left unwalked / the ones a later step rolled back / the ones behind the first job the table says ends differently from its prediction
                     // (held != 0 only while the last job of `hot` is one the table says is predicted wrong: KFL_CUT is the only place that fills it, and every path that changes the
                     // table, or that job's outcome, either empties it or cuts again.  The jobs of a run are hot | held | the ones walked | rest at any time.)
-                    int c0 = 0, c1 = 0, jj; uint32_t w;
+                    int c0 = 0, c1 = 0, c2 = 0, nx = 0, jj; uint32_t w;  // (nx, lane jj: the commands gang jj holds beyond its second)
                     if (nz != nz_tab) { KFL_TABLE(); }  // (a new stretch, or a long gang changed the mask)
                     KFL_CUT(hot);
                     do {
@@ -298,10 +304,14 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                                 // the counts in front of the gang: the first step taken back
                                 int cnt_s = kw::writelane(cnt, t2, g2); cnt_s = kw::writelane(cnt_s, cg, g);
                                 KFL_STEP(B, KFL_HOLD1);
+                                // further steps, in place: each one's lower word into the next held register.  cnt_s / nz_s, kept once, stand for the state in front of the gang
+                                // whichever step finds no level or runs out of registers
+                                int more = 0;
+                                if constexpr (HELD >= 3) { if (ok && placed < nt) { KFL_STEP(C, KFL_HOLD2); more = 1; } }
                                 if (!ok) { cnt = cnt_s; nz = nz_s; extra += placed; fail2 |= 1ull << jj; }  // Statement.Rollback: it booked the tasks it placed and the one that found no node
-                                else if (placed < nt) {  // a third step: not in lanes — the run ends in front of this gang, which then goes the long way (no outcome here: it counts as predicted right and is taken out of `walked` below)
+                                else if (placed < nt) {  // one step more than the lanes hold: the run ends in front of this gang, which then goes the long way from the start (no outcome here: it counts as predicted right and is taken out of `walked` below)
                                     cnt = cnt_s; nz = nz_s; longm |= 1ull << jj; rest = hot | held | (1ull << jj); hot = 0; held = 0; ok = pred;
-                                } else twor |= 1ull << jj;
+                                } else { twor |= 1ull << jj; if constexpr (HELD >= 3) nx = kw::writelane(nx, more, jj); }
                                 w = (w & ~(1u << 30)) | ((uint32_t)(pred ^ ok) << 30);
                             }
                             if ((w >> 30) & 1) { hot = 0; held = 0; }  // a job that ends differently from its prediction is the round's last: nothing behind it is walked
@@ -320,13 +330,15 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
                     okm |= okr;
                     if (mismatch) last_jj = 63 - __builtin_clzll(walked);
                     if (okr) {
-                        const int n_my = (int)((okr >> lane) & 1ull) + (int)((twor >> lane) & 1ull);
+                        const int n_my = (int)((okr >> lane) & 1ull) + (int)((twor >> lane) & 1ull) + (HELD >= 3 ? nx : 0);  // 1 .. HELD commands (nx != 0 only in a lane of twor)
                         const int incl = kw::wave_scan_add(n_my), n_run = kw::bcast(incl, 63);
                         KFL_ROOM(n_run);
                         const int pos = wp + incl - n_my;
                         const uint32_t jb = (uint32_t)lane << KFL_JOB_SHIFT;
                         if (n_my >= 1) L.ring[pos & (KFL_RING - 1)] = (uint64_t)(((uint32_t)c0 & 0x7fffffu) | jb) | ((uint64_t)(uint32_t)s.first << 32);
-                        if (n_my >= 2) L.ring[(pos + 1) & (KFL_RING - 1)] = (uint64_t)((uint32_t)c1 | jb) | ((uint64_t)(uint32_t)(s.first + ((c0 >> 12) & 0x7ff) * ((c0 >> 8) & 15)) << 32);
+                        int tb_n = s.first + ((c0 >> 12) & 0x7ff) * ((c0 >> 8) & 15);  // a command's task base: the one before it plus k·per of the held word before it
+                        if (n_my >= 2) L.ring[(pos + 1) & (KFL_RING - 1)] = (uint64_t)((uint32_t)c1 | jb) | ((uint64_t)(uint32_t)tb_n << 32);
+                        if constexpr (HELD >= 3) { tb_n += ((c1 >> 12) & 0x7ff) * ((c1 >> 8) & 15); if (n_my >= 3) L.ring[(pos + 2) & (KFL_RING - 1)] = (uint64_t)((uint32_t)c2 | jb) | ((uint64_t)(uint32_t)tb_n << 32); }
                         wp += n_run;
                         kw::lds_store_rel(&L.head, wp); pub = wp;
                     }
@@ -392,6 +404,7 @@ KW_BODY void kb_fill_levels_t(const KaiCtx& c, RoundParams rp, BucketParams bp) 
         #undef KFL_TABLE
         #undef KFL_CUT
         #undef KFL_HOLD1
+        #undef KFL_HOLD2
         #undef KFL_GANG_END
         if (lane == 0) L.fin = n_done;
         kw::lds_store_rel(&L.head, wp);
