@@ -644,8 +644,8 @@ int kai_job_order(kai_core* core, const kai_job_order_params* params,
  * kai_job_order and every later action, kai_ops_apply or kai_session_update* are as if it had not happened.  It re-derives what every action's own init
  * re-derives before anything reads it: the tasks-to-allocate chunks of the queried jobs where their cache is invalid, and — on the engine path — the scratch
  * tables of the domain tree (free resources, allocatable pods, ratios, keys), the order of the children inside a sibling set (every subSetNodesFn of an action
- * sorts the sets it reads first) and the slots of the preferred-level node scores.  The scores themselves (calculateNodeScores) are NOT returned and NOT left
- * behind for kai_best_nodes / kai_ordered_nodes: a query there is scored without a topology term.  Out of scope of this call.
+ * sorts the sets it reads first) and the slots of the preferred-level node scores.  The scores themselves (calculateNodeScores) are returned by kai_subset_nodes_scored
+ * (below) and taken by kai_ordered_nodes_scored; this call returns none, and kai_best_nodes / kai_ordered_nodes score without a topology term.
  * Two paths, the same answer.  Chip-wide (KAI_SUBSET_PATH_WIDE): a workgroup per query surveys the nodes, rolls the sums up the tree in a table of its own, ranks
  * the siblings and lists the fitting domains; taken for the whole call when the topology plugin is loaded, the session's quantities add exactly in any order,
  * there are no shared-GPU requests and no MIG rows, and every topology has at most 8 levels and paths that fit 63 bits ((domains + topologies)^levels).
@@ -681,6 +681,54 @@ int kai_subset_nodes(kai_core* core, const kai_subset_params* params,
                      kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out,
                      uint32_t* bitmaps_out /* [sets_cap][ceil(N/32)] or NULL */,
                      kai_subset_result* result /* may be NULL */);
+
+/* kai_subset_nodes with the topology plugin's node scores: what t.subGroupNodeScores[subGroup] holds when subSetNodesFn returns (plugins/topology/job_filtering.go:87-90,
+ * calculateNodeScores, node_scoring.go:37-53).  Every output of kai_subset_nodes comes back byte for byte as that call returns it for the same arguments: the same two
+ * paths with the same qualification, KAI_SUBSET_ENGINE_PATH, the same refusals in the same precedence; the call changes nothing in the session either.  Per query it adds
+ *  - score_rows_out[i].level_row: the row of the snapshot's node_domain a node's domain is read from, topo_level_off[t] + preferredLevel, where scores were recorded:
+ *    exactly when the function gets past checkJobDomainFit on the common domain with a preferred level set — decided in front of the level checks, so a query that ends
+ *    KAI_SUBSET_BAD_LEVEL because of its required level, or KAI_SUBSET_NO_FIT on the relevant levels, still has scores.  n_scored: the preferred-level domains in the
+ *    common domain's sub-tree.
+ *  - deciles_out[i * n_domains + d] = floor((idx + 1) / n_scored * 10) (0 .. 10, the reference's arithmetic in double) for such a domain d, in the caller's domain
+ *    indices, at place idx of getLevelDomains' depth-first order over the children as sortTreeFromRoot left them (ratio descending, domain_id_rank ascending);
+ *    KAI_TOPO_NO_SCORE for every other domain.  A node's score is decile x KAI_TOPO_SCORE_UNIT: decile 0 is a score (0.0), 255 is none.  A common domain that is itself
+ *    at the preferred level: one domain, decile 10.
+ *  - {KAI_TOPO_SCORES_NONE, 0} and a row of 255 where the function records nothing: no topology plugin, no constraint, topology -2, no task, a common domain that does not
+ *    fit, no preferred level.  The reference then looks at the sub-group's ancestors (getRelevantNodeScores, node_scoring.go:88-99).  WHICH ROW A TASK USES IS THE
+ *    CALLER'S CHOICE: its pod-set's row, else the nearest ancestor group's that is not NONE; scores are computed once per sub-group and not again between the tasks of a gang.
+ *  - {KAI_TOPO_SCORES_EMPTY, 0} and a row of 255 for a preferred level the topology does not have: the reference stores an empty map and every node fails the lookup.
+ * Additional refusal: NULL score_rows_out or deciles_out with n_queries > 0 is KAI_ERR_INVALID_ARG.  On KAI_ERR_CAPACITY the two outputs stay untouched, like the others. */
+#define KAI_TOPO_SCORE_UNIT   10000.0   /* scores.Topology */
+#define KAI_TOPO_NO_SCORE     255       /* decile of a domain whose nodes have no score: such a node is dropped from the list */
+#define KAI_TOPO_SCORES_NONE  (-1)      /* level_row: the call left no scores for this sub-group (term 0, no node dropped) */
+#define KAI_TOPO_SCORES_EMPTY (-2)      /* level_row: scores were recorded but the preferred level is none of the topology's: every node is dropped */
+typedef struct kai_topo_score_row { int32_t level_row; int32_t n_scored; } kai_topo_score_row;
+int kai_subset_nodes_scored(kai_core* core, const kai_subset_params* params,
+                            const kai_subset_query* queries, int32_t n_queries,
+                            const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                            kai_subset_answer* answers_out /* [n_queries] */,
+                            kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out,
+                            uint32_t* bitmaps_out /* [sets_cap][ceil(N/32)] or NULL */,
+                            kai_topo_score_row* score_rows_out /* [n_queries] */, uint8_t* deciles_out /* [n_queries][n_domains] */,
+                            kai_subset_result* result /* may be NULL */);
+
+/* kai_ordered_nodes with the topology plugin's term (nodeOrderFn, plugins/topology/node_scoring.go:17-35).  queries[i].scores names a row of score_rows / deciles
+ * (n_score_rows rows, deciles [n_score_rows][n_domains], as kai_subset_nodes_scored wrote them), -1 = none.  With scores = s >= 0 and score_rows[s].level_row >= 0,
+ * node n of the node set has the domain dd = node_domain[level_row][n]: with dd < 0 or deciles[s][dd] == KAI_TOPO_NO_SCORE the node is dropped from the list (a node
+ * without a score raises an error in the reference and OrderedNodesByTask drops it, framework/session.go:247-251); otherwise its score is kai_ordered_nodes' score plus
+ * deciles[s][dd] x KAI_TOPO_SCORE_UNIT — the rule the allocate action applies on the device.  level_row == KAI_TOPO_SCORES_EMPTY: n_out[i] = 0.  scores = -1, a
+ * KAI_TOPO_SCORES_NONE row, or a configuration without KAI_PLUGIN_TOPOLOGY: the query is answered exactly as kai_ordered_nodes answers it.
+ * Everything else is kai_ordered_nodes': the bin-pack pre-order range is taken once over the WHOLE node set, dropped nodes included (NodePreOrderFn runs before any
+ * score); is_pipeline; n_out and the {-1, 0} tail; k = 1 .. KAI_ORDERED_MAX_K (k = 1 is "kai_best_nodes_scored"); duplicates allowed; no look at the pod's status;
+ * sessions with shared GPUs / MIG are served; one staging upload (the score rows and deciles ride in it), three launches, one download, one synchronise.
+ * Refusals, decided before the first device call, outputs untouched: everything kai_ordered_nodes refuses (there is no pad field); scores outside -1 .. n_score_rows-1;
+ * a negative n_score_rows; NULL score_rows / deciles with n_score_rows > 0; a level_row outside -2 .. n_topo_levels-1; a decile that is neither <= 10 nor 255.
+ * n_queries == 0: KAI_OK without a launch. */
+typedef struct kai_scored_query { int32_t pod; int32_t nodeset; uint32_t flags; int32_t scores; } kai_scored_query;  /* scores: row of score_rows / deciles, -1 = none */
+int kai_ordered_nodes_scored(kai_core* core, const kai_scored_query* queries, int32_t n_queries,
+                             const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                             const kai_topo_score_row* score_rows, const uint8_t* deciles, int32_t n_score_rows,
+                             int32_t k, kai_node_answer* out /* [n_queries][k] */, int32_t* n_out /* [n_queries] */);
 
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);

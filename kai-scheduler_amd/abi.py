@@ -302,6 +302,21 @@ class KaiSubsetResult(C.Structure):
     _fields_ = [("n_sets", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
 
 
+TOPO_SCORE_UNIT = 10000.0                         # KAI_TOPO_SCORE_UNIT: scores.Topology, a node's score is decile x this
+TOPO_NO_SCORE = 255                               # KAI_TOPO_NO_SCORE: decile of a domain whose nodes have no score
+TOPO_SCORES_NONE, TOPO_SCORES_EMPTY = -1, -2      # kai_topo_score_row.level_row: no scores left for the sub-group / recorded, but no node has one
+
+
+class KaiTopoScoreRow(C.Structure):
+    """kai_topo_score_row: the node_domain row a node's domain is read from (or TOPO_SCORES_NONE / _EMPTY) and the number of scored domains."""
+    _fields_ = [("level_row", C.c_int32), ("n_scored", C.c_int32)]
+
+
+class KaiScoredQuery(C.Structure):
+    """kai_scored_query: kai_node_query with `scores`, the row of the call's score rows / deciles (-1 = none), in place of pad."""
+    _fields_ = [("pod", C.c_int32), ("nodeset", C.c_int32), ("flags", C.c_uint32), ("scores", C.c_int32)]
+
+
 class KaiQueueShare(C.Structure):
     _fields_ = [(n, C.c_double * 3) for n in ("fair_share", "allocated", "allocated_non_preemptible", "request", "deserved", "max_allowed")]
 

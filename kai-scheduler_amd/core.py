@@ -21,10 +21,11 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes", "kai_subset_nodes_scored", "kai_ordered_nodes_scored",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
+_SCORE_ROW_DTYPE = np.dtype([("level_row", "<i4"), ("n_scored", "<i4")])  # kai_topo_score_row
 _OP_DTYPE = np.dtype([("seq", "<i8"), ("kind", "<i4"), ("pod", "<i4"), ("node", "<i4"), ("job", "<i4"), ("stmt", "<i4"), ("pad", "<i4")])  # kai_op (include/kai_core.h)
 
 
@@ -132,6 +133,11 @@ def load_library(path: str = LIB_PATH):
                                   C.POINTER(abi.KaiJobOrderResult)]
     lib.kai_subset_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiSubsetParams), C.POINTER(abi.KaiSubsetQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiSubsetAnswer),
                                      C.POINTER(abi.KaiNodeSet), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(abi.KaiSubsetResult)]
+    lib.kai_subset_nodes_scored.argtypes = [C.c_void_p, C.POINTER(abi.KaiSubsetParams), C.POINTER(abi.KaiSubsetQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiSubsetAnswer),
+                                            C.POINTER(abi.KaiNodeSet), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(abi.KaiTopoScoreRow), C.POINTER(C.c_uint8),
+                                            C.POINTER(abi.KaiSubsetResult)]
+    lib.kai_ordered_nodes_scored.argtypes = [C.c_void_p, C.POINTER(abi.KaiScoredQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiTopoScoreRow), C.POINTER(C.c_uint8), C.c_int32,
+                                             C.c_int32, C.POINTER(abi.KaiNodeAnswer), C.POINTER(C.c_int32)]
     lib.kai_pod_states.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     lib.kai_node_states.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeState), C.c_int]
     lib.kai_action_stats_get.argtypes = [C.c_void_p, C.POINTER(abi.KaiActionStats)]
@@ -352,6 +358,26 @@ class Session:
                                                          out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer)), count.ctypes.data_as(C.POINTER(C.c_int32))))
         return out["node"].copy(), out["is_pipeline"].astype(bool), count[:M]
 
+    def ordered_nodes_scored(self, pods, k, nodesets=None, nodeset_of=None, score_rows=None, deciles=None, scores_of=None, pipeline_only=None):
+        """kai_ordered_nodes_scored: ordered_nodes with the topology plugin's node scores.  score_rows, deciles: what subset_nodes_scored returned (any rows of it, in
+        any order); scores_of: per pod its row in them (-1 / None = none: the pod is answered as ordered_nodes answers it).  A node whose domain at the row's level has
+        no score is dropped; the others get decile x abi.TOPO_SCORE_UNIT on top of their score.  Returns what ordered_nodes returns."""
+        q, words, n_sets = self._node_queries(pods, nodesets, nodeset_of, pipeline_only)
+        M, k = len(q), int(k)
+        D = int(self.snap.arrays["domain_level"].shape[0]) if "domain_level" in self.snap.arrays else 0  # n_domains
+        rows = np.zeros(0, _SCORE_ROW_DTYPE) if score_rows is None else np.ascontiguousarray(score_rows, dtype=_SCORE_ROW_DTYPE).ravel()
+        dec = np.ascontiguousarray(np.zeros((len(rows), D), np.uint8) if deciles is None else deciles, dtype=np.uint8).reshape(len(rows), D)
+        q["pad"] = -1 if scores_of is None else np.array([-1 if s is None else int(s) for s in np.asarray(scores_of, dtype=object).ravel()], dtype=np.int32)  # kai_scored_query.scores
+        out = np.zeros((M, max(k, 1)), dtype=np.dtype([("node", "<i4"), ("is_pipeline", "<i4")]))  # kai_node_answer
+        count = np.zeros(max(M, 1), np.int32)
+        pad = np.zeros(1, np.uint8)  # (an array without elements has no address to pass)
+        self.core._check(self.core.lib.kai_ordered_nodes_scored(self.core.handle, q.ctypes.data_as(C.POINTER(abi.KaiScoredQuery)), M,
+                                                                words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_sets else None, n_sets,
+                                                                rows.ctypes.data_as(C.POINTER(abi.KaiTopoScoreRow)) if len(rows) else None,
+                                                                (dec if dec.size else pad).ctypes.data_as(C.POINTER(C.c_uint8)) if len(rows) else None, len(rows), k,
+                                                                out.ctypes.data_as(C.POINTER(abi.KaiNodeAnswer)), count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out["node"].copy(), out["is_pipeline"].astype(bool), count[:M]
+
     def apply_ops(self, ops, check_only: bool = False, engine_path: bool = False):
         """kai_ops_apply: committed operations taken back into the session, as framework.Statement applies and commits them — `ops` is the array `execute` returns
         (of this or another handle), or any array of kai_op records (seq and job are not read).  check_only: validate, write nothing; engine_path: take the engine
@@ -402,6 +428,18 @@ class Session:
         Returns (answers, sets, masks, result): the kai_subset_answer and kai_node_set records as structured arrays (the sets of query i are
         sets[answers["first"][i] : answers["first"][i] + answers["n_sets"][i]], in the order the action tries them), the sets' nodes as a bool array [n_sets, N]
         (None without bitmaps; a row can be passed as a node set of best_nodes / ordered_nodes), and the kai_subset_result."""
+        return self._subset_nodes(False, jobs, groups, podsets, nodesets, nodeset_of, engine_path, bitmaps)
+
+    def subset_nodes_scored(self, jobs, groups=None, podsets=None, nodesets=None, nodeset_of=None, engine_path: bool = False, bitmaps: bool = True):
+        """kai_subset_nodes_scored: subset_nodes with the topology plugin's node scores.  Returns (answers, sets, masks, score_rows, deciles, result): the first three and the
+        last as subset_nodes returns them; score_rows: a structured array (level_row, n_scored) per query — level_row the node_domain row a node's domain is read from,
+        abi.TOPO_SCORES_NONE where the reference records nothing for the sub-group (a task then uses the nearest ancestor group's row that is not NONE: the caller's
+        choice), abi.TOPO_SCORES_EMPTY for a preferred level the topology does not have; deciles: uint8 [M, n_domains], floor((idx + 1) / n_scored * 10) for the scored
+        domains, abi.TOPO_NO_SCORE elsewhere.  Both go into ordered_nodes_scored as they are."""
+        return self._subset_nodes(True, jobs, groups, podsets, nodesets, nodeset_of, engine_path, bitmaps)
+
+    def _subset_nodes(self, scored, jobs, groups, podsets, nodesets, nodeset_of, engine_path, bitmaps):
+        """The call subset_nodes and subset_nodes_scored share (scored: with the score rows and deciles)."""
         jobs = np.ascontiguousarray(jobs, dtype=np.int32).ravel()
         M, N = len(jobs), self.snap.n_nodes
         W = max((N + 31) // 32, 1)
@@ -414,12 +452,16 @@ class Session:
         params = abi.KaiSubsetParams(abi.SUBSET_VERSION, abi.SUBSET_ENGINE_PATH if engine_path else 0)
         n, res = C.c_int64(0), abi.KaiSubsetResult()
         cap = max(64, 8 * M)
+        D = int(self.snap.arrays["domain_level"].shape[0]) if "domain_level" in self.snap.arrays else 0  # n_domains
+        score_rows, deciles = np.zeros(max(M, 1), _SCORE_ROW_DTYPE), np.zeros((max(M, 1), max(D, 1)), np.uint8)
+        tail = (score_rows.ctypes.data_as(C.POINTER(abi.KaiTopoScoreRow)), deciles.ctypes.data_as(C.POINTER(C.c_uint8))) if scored else ()
+        fn = self.core.lib.kai_subset_nodes_scored if scored else self.core.lib.kai_subset_nodes
         for _ in range(2):  # the capacity protocol: where the first guess is too small the call says how many there are, and the second call has room
             sets = np.zeros(max(cap, 1), set_dt)
             maps = np.zeros((max(cap, 1), W), np.uint32) if bitmaps else None
-            rc = self.core.lib.kai_subset_nodes(self.core.handle, C.byref(params), q.ctypes.data_as(C.POINTER(abi.KaiSubsetQuery)), M,
-                                                words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_rows else None, n_rows, ans.ctypes.data_as(C.POINTER(abi.KaiSubsetAnswer)),
-                                                sets.ctypes.data_as(C.POINTER(abi.KaiNodeSet)), cap, C.byref(n), maps.ctypes.data_as(C.POINTER(C.c_uint32)) if bitmaps else None, C.byref(res))
+            rc = fn(self.core.handle, C.byref(params), q.ctypes.data_as(C.POINTER(abi.KaiSubsetQuery)), M,
+                    words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_rows else None, n_rows, ans.ctypes.data_as(C.POINTER(abi.KaiSubsetAnswer)),
+                    sets.ctypes.data_as(C.POINTER(abi.KaiNodeSet)), cap, C.byref(n), maps.ctypes.data_as(C.POINTER(C.c_uint32)) if bitmaps else None, *tail, C.byref(res))
             if rc != -4 or n.value <= cap:  # KAI_ERR_CAPACITY
                 break
             cap = int(n.value)
@@ -429,6 +471,8 @@ class Session:
         if bitmaps:
             bits = (maps[:total, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
             masks = bits.reshape(total, W * 32)[:, :N].astype(bool)
+        if scored:
+            return ans[:M], sets[:total].copy(), masks, score_rows[:M], np.ascontiguousarray(deciles[:M, :D]), res
         return ans[:M], sets[:total].copy(), masks, res
 
     def gpu_groups(self):

@@ -185,16 +185,18 @@ __global__ void __launch_bounds__(KAI_BN_WG) k_bn_scan(KaiCtx c, BnArgs a) { bn_
 #endif
 
 // Where the pieces of one call lie in the handle's scratch (device) and staging (pinned host) buffers, 16-byte aligned.  The permutation comes first, at an offset no call
-// moves; [queries | rows_in | need] is what every call sends, in ONE copy (with the permutation in front of it on the first call of a session).
+// moves; [queries | rows_in | need] is what every call sends, in ONE copy (with the permutation in front of it on the first call of a session).  extra_up: bytes a call
+// sends on top (kai_ordered_nodes_scored: its score rows and deciles), behind `need` in the same copy.
 struct BnLayout {
-    size_t perm, queries, rows_in, need, up_end, rows, range, prep, out, end;
-    BnLayout(int N, int M, int S, int W) {
+    size_t perm, queries, rows_in, need, extra, up_end, rows, range, prep, out, end;
+    BnLayout(int N, int M, int S, int W, size_t extra_up = 0) {
         auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
         size_t o = 0;
         perm = o; o = al(o + (size_t)(N > 0 ? N : 1) * 4);
         queries = o; o = al(o + (size_t)M * sizeof(kai_node_query));
         rows_in = o; o = al(o + (size_t)S * W * 4 + 4);
         need = o; o = al(o + (size_t)2 * (S + 1) * 4);
+        extra = o; o = al(o + extra_up);
         up_end = o;
         rows = o; o = al(o + (size_t)S * W * 4 + 4);
         range = o; o = al(o + (size_t)2 * (S + 1) * 2 * 8);

@@ -151,8 +151,9 @@ int kai_best_node(kai_core* core, int32_t pod_idx, const uint32_t* nodeset_bitma
     return KAI_OK;
 }
 
-// What kai_best_nodes and kai_ordered_nodes refuse alike, in one pass and before the first device call.  *empty: an accepted call without queries (KAI_OK, nothing to do)
-static int bn_check(kai_core* core, const char* who, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, bool out_null, bool* empty) {
+// What kai_best_nodes, kai_ordered_nodes and kai_ordered_nodes_scored refuse alike, in one pass and before the first device call.  *empty: an accepted call without queries
+// (KAI_OK, nothing to do).  n_score_rows >= 0: the queries are kai_scored_query (the same layout): the fourth word names a score row, -1 = none, instead of being a pad.
+static int bn_check(kai_core* core, const char* who, const kai_node_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets, bool out_null, bool* empty, int32_t n_score_rows = -1) {
     auto no = [&](int code, const char* why) { core->err = std::string(who) + ": " + why; return code; };
     *empty = false;
     if (n_queries < 0 || n_nodesets < 0) return no(KAI_ERR_INVALID_ARG, "a negative count");
@@ -167,14 +168,15 @@ static int bn_check(kai_core* core, const char* who, const kai_node_query* queri
         if (q.pod < 0 || q.pod >= P) return no(KAI_ERR_INVALID_ARG, "pod index out of range");
         if (q.nodeset < -1 || q.nodeset >= S) return no(KAI_ERR_INVALID_ARG, "nodeset outside -1 .. n_nodesets-1");
         if (q.flags & ~KAI_QUERY_PIPELINE_ONLY) return no(KAI_ERR_INVALID_ARG, "unknown flag bits");
-        if (q.pad != 0) return no(KAI_ERR_INVALID_ARG, "pad is not zero");
+        if (n_score_rows < 0 ? q.pad != 0 : (q.pad < -1 || q.pad >= n_score_rows)) return no(KAI_ERR_INVALID_ARG, n_score_rows < 0 ? "pad is not zero" : "scores outside -1 .. n_score_rows-1");
     }
     return KAI_OK;
 }
 
 // The part of a call the two share: the handle's scratch (dev_bytes) and staging ([what is sent][down_bytes of answers]) grown on demand — the only allocations, none once the
 // handle is warm —, ONE staging upload and the launches of k_bn_prep and k_bn_range.  The permutation lies at offset 0 of the scratch whichever of the two calls sized it.
-static int bn_stage(kai_core* core, const BnLayout& L, size_t dev_bytes, size_t down_bytes, const kai_node_query* queries, const uint32_t* nodeset_bitmaps, int M, int S, int W, BnArgs& a) {
+static int bn_stage(kai_core* core, const BnLayout& L, size_t dev_bytes, size_t down_bytes, const kai_node_query* queries, const uint32_t* nodeset_bitmaps, int M, int S, int W, BnArgs& a,
+                    const void* extra0 = nullptr, size_t extra0_bytes = 0, const void* extra1 = nullptr, size_t extra1_bytes = 0) {
     const int N = core->ctx.N;
     bool grew = false;
     KAI_TRY(reserve(core, core->bn_dev, dev_bytes, std::max<size_t>(dev_bytes + dev_bytes / 2, (size_t)1 << 16), &grew));
@@ -188,6 +190,8 @@ static int bn_stage(kai_core* core, const BnLayout& L, size_t dev_bytes, size_t 
     std::memcpy(h + L.queries, queries, (size_t)M * sizeof(kai_node_query));
     if (S > 0 && W > 0) std::memcpy(h + L.rows_in, nodeset_bitmaps, (size_t)S * W * 4);
     std::memset(h + L.need, 0, L.up_end - L.need);
+    if (extra0_bytes) std::memcpy(h + L.extra, extra0, extra0_bytes);  // (what a scored call sends on top: [score rows | deciles], in the same copy)
+    if (extra1_bytes) std::memcpy(h + L.extra + ((extra0_bytes + 15) & ~(size_t)15), extra1, extra1_bytes);
     HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, L.up_end - up0, hipMemcpyHostToDevice, core->stream));
     core->bn_perm_ok = true;
     a = BnArgs{};
@@ -248,6 +252,48 @@ int kai_ordered_nodes(kai_core* core, const kai_node_query* queries, int32_t n_q
     o.k = k; o.out = (KAI_GP(kai_node_answer))(core->bn_dev.p + L.lists); o.n_out = (KAI_GP(int32_t))(core->bn_dev.p + L.n_out);
     const int grid = std::min(M, cus * KAI_BN_WGS_PER_CU);
     hipLaunchKernelGGL(k_on_scan, dim3((unsigned)grid), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a, o);
+    HIP_TRY(core, hipGetLastError());
+    // ---- one download ([the lists | their lengths]), one synchronise
+    unsigned char* h_out = core->bn_pin.p + L.up_end;
+    HIP_TRY(core, hipMemcpyAsync(h_out, core->bn_dev.p + L.lists, L.down_bytes(M, k), hipMemcpyDeviceToHost, core->stream));
+    HIP_TRY(core, hipStreamSynchronize(core->stream));
+    std::memcpy(out, h_out, (size_t)M * k * sizeof(kai_node_answer));
+    std::memcpy(n_out, h_out + (L.n_out - L.lists), (size_t)M * 4);
+    return KAI_OK;
+}
+
+int kai_ordered_nodes_scored(kai_core* core, const kai_scored_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                             const kai_topo_score_row* score_rows, const uint8_t* deciles, int32_t n_score_rows, int32_t k, kai_node_answer* out, int32_t* n_out) {
+    // every refusal before the first device call; `out` and `n_out` are written only after the lists came back
+    if (!core) return KAI_ERR_INVALID_ARG;
+    if (k < 1 || k > KAI_ORDERED_MAX_K) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes_scored: k outside 1 .. KAI_ORDERED_MAX_K");
+    if (n_score_rows < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes_scored: a negative n_score_rows");
+    if (n_score_rows > 0 && (!score_rows || !deciles)) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes_scored: score_rows / deciles is NULL");
+    bool empty = false;
+    const kai_node_query* nq = reinterpret_cast<const kai_node_query*>(queries);  // (the same layout: kai_ordered_nodes.hpp asserts it)
+    KAI_TRY(bn_check(core, "kai_ordered_nodes_scored", nq, n_queries, nodeset_bitmaps, n_nodesets, !out || !n_out, &empty, n_score_rows));
+    const int D = core->ctx.D, TL = core->ctx.TL;
+    for (int s = 0; s < n_score_rows; s++) {  // one host pass over the rows
+        if (score_rows[s].level_row < KAI_TOPO_SCORES_EMPTY || score_rows[s].level_row >= TL) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes_scored: a level_row outside -2 .. n_topo_levels-1");
+        const uint8_t* row = deciles + (size_t)s * D;
+        for (int d = 0; d < D; d++) if (row[d] > 10 && row[d] != KAI_TOPO_NO_SCORE) return fail(core, KAI_ERR_INVALID_ARG, "kai_ordered_nodes_scored: a decile that is neither <= 10 nor 255");
+    }
+    if (empty) return KAI_OK;
+    if ((int64_t)n_queries * k > ((int64_t)1 << 27)) return fail(core, KAI_ERR_CAPACITY, "kai_ordered_nodes_scored: n_queries * k above 2^27");
+    if ((int64_t)n_score_rows * (D + 8) > ((int64_t)1 << 30)) return fail(core, KAI_ERR_CAPACITY, "kai_ordered_nodes_scored: n_score_rows x (n_domains + 8) above 2^30");
+    const int N = core->ctx.N, M = n_queries, S = n_nodesets, W = (N + 31) / 32;
+    HIP_TRY(core, hipSetDevice(core->device));
+    const size_t row_bytes = (size_t)n_score_rows * sizeof(kai_topo_score_row), dec_bytes = (size_t)n_score_rows * D, dec_off = (row_bytes + 15) & ~(size_t)15;
+    const OnLayout L(N, M, S, W, k, dec_off + dec_bytes);
+    const int cus = device_cus(core);
+    BnArgs a;
+    KAI_TRY(bn_stage(core, L, L.on_end, L.down_bytes(M, k), nq, nodeset_bitmaps, M, S, W, a, score_rows, row_bytes, deciles, dec_bytes));  // the upload and two of the three launches
+    OnArgs o{};
+    o.k = k; o.out = (KAI_GP(kai_node_answer))(core->bn_dev.p + L.lists); o.n_out = (KAI_GP(int32_t))(core->bn_dev.p + L.n_out);
+    OnScoreArgs sa{};
+    sa.D = D; sa.rows = (KAI_GP(const kai_topo_score_row))(core->bn_dev.p + L.extra); sa.deciles = (KAI_GP(const uint8_t))(core->bn_dev.p + L.extra + dec_off);
+    const int grid = std::min(M, cus * KAI_BN_WGS_PER_CU);
+    hipLaunchKernelGGL(k_on_scan_scored, dim3((unsigned)grid), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a, o, sa);
     HIP_TRY(core, hipGetLastError());
     // ---- one download ([the lists | their lengths]), one synchronise
     unsigned char* h_out = core->bn_pin.p + L.up_end;
@@ -575,13 +621,13 @@ struct SnLauncher : ProfLauncher {
     }
 };
 
-extern "C" {
-
-int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_subset_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
-                     kai_subset_answer* answers_out, kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out, uint32_t* bitmaps_out, kai_subset_result* result) {
+// kai_subset_nodes and kai_subset_nodes_scored (scored: with the preferred-level scores into score_rows_out / deciles_out)
+static int subset_nodes_call(kai_core* core, const char* who, bool scored, const kai_subset_params* params, const kai_subset_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps,
+                             int32_t n_nodesets, kai_subset_answer* answers_out, kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out, uint32_t* bitmaps_out,
+                             kai_topo_score_row* score_rows_out, uint8_t* deciles_out, kai_subset_result* result) {
     // every refusal before the first device call and before the first write to the caller's arrays
     if (!core) return KAI_ERR_INVALID_ARG;
-    auto no = [&](int code, const char* why) { core->err = std::string("kai_subset_nodes: ") + why; return code; };
+    auto no = [&](int code, const char* why) { core->err = std::string(who) + ": " + why; return code; };
     if (!params || !n_sets_out) return no(KAI_ERR_INVALID_ARG, "params / n_sets_out is NULL");
     if (params->version != KAI_SUBSET_VERSION) return no(KAI_ERR_INVALID_ARG, "wrong params version");
     if (params->flags & ~KAI_SUBSET_ENGINE_PATH) return no(KAI_ERR_INVALID_ARG, "unknown flag bits");
@@ -589,6 +635,7 @@ int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_
     if (n_queries > 0 && (!queries || !answers_out)) return no(KAI_ERR_INVALID_ARG, "queries / answers_out is NULL");
     if (n_nodesets > 0 && !nodeset_bitmaps) return no(KAI_ERR_INVALID_ARG, "nodeset_bitmaps is NULL");
     if (sets_cap > 0 && !sets_out) return no(KAI_ERR_INVALID_ARG, "sets_out is NULL");
+    if (scored && n_queries > 0 && (!score_rows_out || !deciles_out)) return no(KAI_ERR_INVALID_ARG, "score_rows_out / deciles_out is NULL");
     if (core->world > 1) return no(KAI_ERR_UNSUPPORTED, "a handle of a sharded group");
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
     const KaiCtx& c = core->ctx;
@@ -619,11 +666,11 @@ int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_
     const bool wide = !(params->flags & KAI_SUBSET_ENGINE_PATH) && sn_wide_session(c, core->sn_levels);
     // workgroups of k_sn_wide: as k_bn_scan's grid, and no more than 256 MiB of domain tables
     const int cus = device_cus(core);
-    const size_t table_bytes = (size_t)std::max(DT, 1) * (KAI_MAX_RES * 8 + 8 + 8 + 4 + 4 + 4);
+    const size_t table_bytes = (size_t)std::max(DT, 1) * (KAI_MAX_RES * 8 + 8 + 8 + 4 + 4 + 4 + (scored ? 4 : 0));
     const int wgs = wide ? (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(M, cus * KAI_SN_WGS_PER_CU), ((size_t)256 << 20) / table_bytes)) : 0;
     const int n_children = DT > 0 ? hp.dom_child_off[(size_t)DT] : 0;
     // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
-    const SnLayout L(N, M, S, W, stride, DT, n_children, wgs);
+    const SnLayout L(N, M, S, W, stride, DT, n_children, wgs, scored, c.D);
     bool grew = false;
     KAI_TRY(reserve(core, core->sn_dev, L.end, L.end + L.end / 4, &grew));
     if (grew) core->sn_tab_ok = false;  // (the new scratch does not hold the session's tables)
@@ -644,13 +691,13 @@ int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_
     HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, L.up_end - up0, hipMemcpyHostToDevice, core->stream));
     core->sn_tab_ok = true;
     SnArgs a = sn_bind_args(d, L, M, S, W, stride);
-    a.want_bitmaps = bitmaps_out ? 1 : 0;
+    a.want_bitmaps = bitmaps_out ? 1 : 0; a.want_scores = scored ? 1 : 0;
     KaiCtx cq = c; cq.action = KAI_ACTION_ALLOCATE;  // (the chunk the allocate action hands over)
     // ---- the walks and the count, behind one small download
     SnLauncher launcher(core, h + L.up_end, std::getenv("KAI_SUBSET_PROF") != nullptr);
     SnHead hd{}; int path = KAI_SUBSET_PATH_NONE;
     const int rcd = sn_count(launcher, cq, a, wide, KAI_SN_WG, wgs, hd, path);
-    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[160]; std::snprintf(buf, sizeof buf, "kai_subset_nodes: engine fault code %d (engine source line %d)", hd.fault, hd.fault_line); core->err = buf; return rcd; }
+    if (rcd == KAI_ERR_DEVICE_FAULT) { char buf[160]; std::snprintf(buf, sizeof buf, "%s: engine fault code %d (engine source line %d)", who, hd.fault, hd.fault_line); core->err = buf; return rcd; }
     if (rcd) return rcd;
     const int64_t total = hd.total;
     if (total > sets_cap) { *n_sets_out = total; return no(KAI_ERR_CAPACITY, "sets_cap is below the number of node sets (*n_sets_out holds it)"); }
@@ -662,18 +709,38 @@ int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_
         launcher.emit((int)std::min<int64_t>(total, (int64_t)cus * KAI_SN_WGS_PER_CU), KAI_SN_WG, cq, a);
         HIP_TRY(core, hipGetLastError());
     }
-    const size_t down = ans_bytes + set_bytes + map_bytes;
+    const size_t score_bytes = scored ? L.end - L.score_rows : 0;  // [score_rows | deciles] as they lie in the scratch
+    const size_t down = ans_bytes + set_bytes + map_bytes + score_bytes;
     KAI_TRY(reserve(core, core->sn_pin, down, std::max<size_t>(down + down / 4, (size_t)1 << 16)));  // (what the staging held has been sent)
     h = core->sn_pin.p;
     HIP_TRY(core, hipMemcpyAsync(h, d + L.answers, ans_bytes, hipMemcpyDeviceToHost, core->stream));
     if (total > 0) HIP_TRY(core, hipMemcpyAsync(h + ans_bytes, core->sn_out.p, set_bytes + map_bytes, hipMemcpyDeviceToHost, core->stream));
+    if (score_bytes) HIP_TRY(core, hipMemcpyAsync(h + ans_bytes + set_bytes + map_bytes, d + L.score_rows, score_bytes, hipMemcpyDeviceToHost, core->stream));
     HIP_TRY(core, hipStreamSynchronize(core->stream));
     launcher.report("kai subset nodes", "sets", path, total);
+    if (scored) {
+        const unsigned char* hs = h + ans_bytes + set_bytes + map_bytes;
+        std::memcpy(score_rows_out, hs, (size_t)M * sizeof(kai_topo_score_row));
+        if (c.D > 0) std::memcpy(deciles_out, hs + (L.deciles - L.score_rows), (size_t)M * (size_t)c.D);
+    }
     std::memcpy(answers_out, h, ans_bytes);
     if (total > 0) { std::memcpy(sets_out, h + ans_bytes, set_bytes); if (bitmaps_out) std::memcpy(bitmaps_out, h + ans_bytes + set_bytes, map_bytes); }
     *n_sets_out = total;
     if (result) { result->n_sets = total; result->path = path; result->pad = 0; }
     return KAI_OK;
+}
+
+extern "C" {
+
+int kai_subset_nodes(kai_core* core, const kai_subset_params* params, const kai_subset_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                     kai_subset_answer* answers_out, kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out, uint32_t* bitmaps_out, kai_subset_result* result) {
+    return subset_nodes_call(core, "kai_subset_nodes", false, params, queries, n_queries, nodeset_bitmaps, n_nodesets, answers_out, sets_out, sets_cap, n_sets_out, bitmaps_out, nullptr, nullptr, result);
+}
+
+int kai_subset_nodes_scored(kai_core* core, const kai_subset_params* params, const kai_subset_query* queries, int32_t n_queries, const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                            kai_subset_answer* answers_out, kai_node_set* sets_out, int64_t sets_cap, int64_t* n_sets_out, uint32_t* bitmaps_out,
+                            kai_topo_score_row* score_rows_out, uint8_t* deciles_out, kai_subset_result* result) {
+    return subset_nodes_call(core, "kai_subset_nodes_scored", true, params, queries, n_queries, nodeset_bitmaps, n_nodesets, answers_out, sets_out, sets_cap, n_sets_out, bitmaps_out, score_rows_out, deciles_out, result);
 }
 
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap) {

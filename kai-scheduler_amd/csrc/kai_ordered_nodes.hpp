@@ -17,8 +17,15 @@
 // loop is bounded by N, M or K (a ballot has 64 bits).  Every cross-lane call is reached by whole wavefronts: the stride's trip count and the loop over a ballot's bits
 // are the same in every lane of a wavefront, and a lane without a node of its own takes part with an empty candidate.  The block size is a multiple of 64.
 //
+// kai_ordered_nodes_scored adds the topology plugin's term (nodeOrderFn, plugins/topology/node_scoring.go:17-35) in k_on_scan_scored, the same body with SCORED set: a query
+// names a row of score rows / deciles (kai_subset_nodes_scored's outputs, sent with the queries); a node's domain at the row's level is one coalesced load of node_domain per
+// stride, its decile a byte gather from the query's row (a few hundred bytes every lane of the workgroup reads: left to the caches).  A node without a score is dropped, the
+// others get decile x 10 000 on top — the rule of CMD_BEST (kai_kernels.hpp).  k_on_scan itself is compiled from SCORED = false and carries none of it.
+//
 // Written against kai_simt.hpp, so that tests/host_sim/ordered_nodes_sim.cpp runs the body with emulated lanes on a machine without a GPU.
 #pragma once
+#include <cstddef>
+
 #include "kai_best_nodes.hpp"
 
 namespace kai {
@@ -32,6 +39,14 @@ struct OnArgs {
     KAI_GP(kai_node_answer) out;  // [M][k]
     KAI_GP(int32_t) n_out;        // [M]
 };
+
+// the score rows of a scored call, [n_rows] and [n_rows][D] (D = the snapshot's domains)
+struct OnScoreArgs {
+    int32_t D, pad;
+    KAI_GP(const kai_topo_score_row) rows;
+    KAI_GP(const uint8_t) deciles;
+};
+static_assert(sizeof(kai_scored_query) == sizeof(kai_node_query) && offsetof(kai_scored_query, scores) == offsetof(kai_node_query, pad), "k_bn_prep reads a scored query as a kai_node_query");
 
 // the list's order: greater key, or equal key and lower name rank (nodes are distinct: a strict order; key 0 = an empty entry, last)
 KAI_HD bool on_beats(uint64_t ka, int32_t na, uint64_t kb, int32_t nb) { return ka > kb || (ka == kb && na < nb); }
@@ -51,12 +66,22 @@ KW_BODY void on_insert(uint64_t& ek, int32_t& en, uint64_t ck, int32_t cn, int k
     }
 }
 
-KW_BODY void on_scan_body(const KaiCtx& c, const BnArgs& a, const OnArgs& o) {
+template <bool SCORED>
+KW_BODY void on_scan_body_t(const KaiCtx& c, const BnArgs& a, const OnArgs& o, const OnScoreArgs& s) {
     KW_SHARED uint64_t l_key[KAI_ON_MAX_WAVES * 64]; KW_SHARED int32_t l_node[KAI_ON_MAX_WAVES * 64];
     const int tid = kw::tid(), lanes = kw::bdim(), lane = kw::lane(), wave = tid >> 6, nw = lanes >> 6, k = o.k;
     for (int i = kw::bid(); i < a.M; i += kw::gdim()) {
         BnQuery pq = a.prep[i];
         KAI_GP(kai_node_answer) out = o.out + (size_t)i * k;
+        int trow = -1; KAI_GP(const uint8_t) dec = nullptr;  // the level row the nodes' domains are read from and the query's deciles; -1: no topology term
+        if (SCORED) {
+            const int sr = a.queries[i].pad;  // (kai_scored_query.scores)
+            if ((c.plugins & KAI_PLUGIN_TOPOLOGY) && sr >= 0) {
+                const int lr = s.rows[sr].level_row;
+                if (lr == KAI_TOPO_SCORES_EMPTY) pq.dead = 1;  // scores were recorded and no node has one: every node is dropped
+                else if (lr >= 0) { trow = lr; dec = s.deciles + (size_t)sr * (size_t)s.D; }
+            }
+        }
         if (pq.dead) {  // the same for every lane
             if (tid < k) { kai_node_answer ans; ans.node = -1; ans.is_pipeline = 0; out[tid] = ans; }
             if (tid == 0) o.n_out[i] = 0;
@@ -69,7 +94,12 @@ KW_BODY void on_scan_body(const KaiCtx& c, const BnArgs& a, const OnArgs& o) {
         for (int base = wave * 64; base < c.N; base += lanes) {  // the trip count is the wavefront's, not the lane's
             const int n = base + lane;
             double sc = 0;
-            const bool ok = n < c.N && (pq.row < 0 || bn_in_row(bits, n)) && scan_node_score(c, q, n, sc);
+            bool ok = n < c.N && (pq.row < 0 || bn_in_row(bits, n)) && scan_node_score(c, q, n, sc);
+            if (SCORED && trow >= 0 && n < c.N) {  // a node without a score is dropped (framework/session.go:247-251)
+                const int dd = c.node_domain[(size_t)trow * c.N + n];
+                const int dv = (ok && dd >= 0 && dd < s.D) ? dec[dd] : KAI_TOPO_NO_SCORE;
+                if (dv == KAI_TOPO_NO_SCORE) ok = false; else sc += dv * KAI_TOPO_SCORE_UNIT;
+            }
             on_insert(ek, en, ok ? bn_orderable(sc) : 0, n, k);
         }
         if (nw > 1) {
@@ -98,14 +128,18 @@ KW_BODY void on_scan_body(const KaiCtx& c, const BnArgs& a, const OnArgs& o) {
     }
 }
 
+KW_BODY void on_scan_body(const KaiCtx& c, const BnArgs& a, const OnArgs& o) { on_scan_body_t<false>(c, a, o, OnScoreArgs{}); }
+KW_BODY void on_scan_scored_body(const KaiCtx& c, const BnArgs& a, const OnArgs& o, const OnScoreArgs& s) { on_scan_body_t<true>(c, a, o, s); }
+
 #if defined(__HIPCC__)
 __global__ void __launch_bounds__(KAI_BN_WG) k_on_scan(KaiCtx c, BnArgs a, OnArgs o) { on_scan_body(c, a, o); }
+__global__ void __launch_bounds__(KAI_BN_WG) k_on_scan_scored(KaiCtx c, BnArgs a, OnArgs o, OnScoreArgs s) { on_scan_scored_body(c, a, o, s); }
 #endif
 
 // kai_ordered_nodes' scratch: kai_best_nodes' layout (the permutation at the same offset, the same upload) with [the lists | their lengths] behind it, one download
 struct OnLayout : BnLayout {
     size_t lists, n_out, on_end;
-    OnLayout(int N, int M, int S, int W, int k) : BnLayout(N, M, S, W) {
+    OnLayout(int N, int M, int S, int W, int k, size_t extra_up = 0) : BnLayout(N, M, S, W, extra_up) {
         auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
         lists = end; n_out = lists + (size_t)M * k * sizeof(kai_node_answer);  // (a multiple of 8: the lengths follow without a gap)
         on_end = al(n_out + (size_t)M * 4);

@@ -48,7 +48,7 @@ struct SnPrep {
 
 struct SnArgs {
     int32_t M, S, W, stride;              // queries, parent rows, words per row, raw records a query can have (domains of the largest topology + 1)
-    int32_t want_bitmaps, pad0, pad1, pad2;
+    int32_t want_bitmaps, want_scores, pad1, pad2;  // want_scores (kai_subset_nodes_scored): the preferred-level scores into score_rows / deciles; 0 = not wanted
     KAI_GP(SnHead) head;
     KAI_GP(const kai_subset_query) queries;  // [M]
     KAI_GP(const uint32_t) rows_in;       // [S][W] the caller's rows, caller's node indices
@@ -62,6 +62,9 @@ struct SnArgs {
     KAI_GP(int32_t) etmp;                 // [stride] engine path: the sets of the running query
     // chip-wide path, [workgroups of k_sn_wide][D + T]: free resources, ratio, path key, allocatable pods, place among the siblings, level if chosen
     KAI_GP(double) w_free; KAI_GP(double) w_ratio; KAI_GP(int64_t) w_key; KAI_GP(int32_t) w_ap; KAI_GP(int32_t) w_place; KAI_GP(int32_t) w_lvl;
+    KAI_GP(int32_t) w_sc;                 // ... and, where scores are wanted, 1 for a preferred-level domain of the common domain's sub-tree
+    KAI_GP(kai_topo_score_row) score_rows;  // [M]       } what t.subGroupNodeScores[subGroup] holds when the reference's function returns, as deciles (kai_core.h);
+    KAI_GP(uint8_t) deciles;              // [M][c.D]  } bound where want_scores is set
     KAI_GP(kai_node_set) sets;            // [total]     } k_sn_emit's outputs, in a buffer of their own
     KAI_GP(uint32_t) bitmaps;             // [total][W]  } (sized once the total is known)
 };
@@ -72,6 +75,9 @@ KAI_HD void sn_answer(const SnArgs& a, int i, int status, int n_sets, int tasks,
     kai_subset_answer o; o.status = status; o.n_sets = n_sets; o.first = 0; o.tasks = tasks; o.common_domain = common; o.pad = 0;
     a.answers[i] = o;
 }
+// calculateNodeScores (node_scoring.go:37-53) without the factor scores.Topology: the reference's arithmetic in double
+KAI_HD uint8_t sn_decile(int idx, int n) { const double score = ((double)(idx + 1) / (double)n) * 10; const double t = (double)(int64_t)score; return (uint8_t)(t > score ? t - 1.0 : t); }
+KAI_HD void sn_score_row(const SnArgs& a, int i, int level_row, int n_scored) { kai_topo_score_row o; o.level_row = level_row; o.n_scored = n_scored; a.score_rows[i] = o; }
 // the sub-group a query names: grp (a SubGroupSet) or ps (a pod-set), and its constraint
 struct SnGroup { int32_t grp, ps, topo, req, pref; };
 KAI_HD SnGroup sn_group(const KaiCtx& c, const kai_subset_query& q) {
@@ -117,25 +123,30 @@ KW_BODY void sn_prep_body(const KaiCtx& c, const SnArgs& a) {
     o.early = n_sets >= 0 ? 1 : 0;
     if (n_sets == 1) { SnRaw r; r.domain = -1; r.alloc_pods = -1; a.raw[(size_t)t * a.stride] = r; }
     a.prep[t] = o;
+    if (a.want_scores) sn_score_row(a, (int)t, KAI_TOPO_SCORES_NONE, 0);  // (the walk overwrites it where the function records scores)
     sn_answer(a, (int)t, status, n_sets > 0 ? n_sets : 0, tasks, KAI_SUBSET_PARENT);
 }
 
 KW_BODY void sn_wide_body(const KaiCtx& c, const SnArgs& a) {
-    KW_SHARED int32_t s_min[KAI_TOPO_SCAN_LEVELS], s_max[KAI_TOPO_SCAN_LEVELS], s_any, s_cnt;
+    KW_SHARED int32_t s_min[KAI_TOPO_SCAN_LEVELS], s_max[KAI_TOPO_SCAN_LEVELS], s_any, s_cnt, s_nsc;
     const int tid = kw::tid(), lanes = kw::bdim(), DT = c.D + c.T, N = c.N, R = c.R;
     NullBackend nb; Engine<NullBackend> eng(c, nb);
     const size_t wb = (size_t)kw::bid() * (size_t)DT;
     KAI_GP(double) fr = a.w_free + wb * KAI_MAX_RES; KAI_GP(double) ratio = a.w_ratio + wb; KAI_GP(int64_t) key = a.w_key + wb;
     KAI_GP(int32_t) ap = a.w_ap + wb; KAI_GP(int32_t) place = a.w_place + wb; KAI_GP(int32_t) lvl = a.w_lvl + wb;
+    const bool ws = a.want_scores != 0;
+    KAI_GP(int32_t) scd = ws ? a.w_sc + wb : nullptr;
     for (int i = kw::bid(); i < a.M; i += kw::gdim()) {
         const SnPrep pq = a.prep[i];
+        KAI_GP(uint8_t) drow = ws ? a.deciles + (size_t)i * (size_t)c.D : nullptr;
+        if (ws) for (int d = tid; d < c.D; d += lanes) drow[d] = KAI_TOPO_NO_SCORE;  // (a lane that stores a decile below stores it behind its own 255)
         if (pq.early) continue;  // (the same for every lane)
         const int t = pq.topo, row0 = c.topo_level_off[t], L = c.topo_level_off[t + 1] - row0, root = c.D + t, tasks = pq.sum.tasks, req = pq.req, pref = pq.pref;
         const bool hom = pq.sum.homogeneous != 0;
         KAI_GP(const uint32_t) parent = a.queries[i].nodeset >= 0 ? a.rows + (size_t)a.queries[i].nodeset * a.W : nullptr;
         auto node_dom = [&](int row, int n) { return c.node_domain[(size_t)row * N + n]; };
         // ---- lowestCommonDomainID (common.go:17-67) over the nodes of the parent row that are part of the topology
-        if (tid == 0) { s_any = 0; s_cnt = 0; for (int l = 0; l < KAI_TOPO_SCAN_LEVELS; l++) { s_min[l] = 0x7fffffff; s_max[l] = -0x7fffffff - 1; } }
+        if (tid == 0) { s_any = 0; s_cnt = 0; s_nsc = 0; for (int l = 0; l < KAI_TOPO_SCAN_LEVELS; l++) { s_min[l] = 0x7fffffff; s_max[l] = -0x7fffffff - 1; } }
         kw::sync();
         {   int mn[KAI_TOPO_SCAN_LEVELS], mx[KAI_TOPO_SCAN_LEVELS]; bool any = false;
             for (int l = 0; l < KAI_TOPO_SCAN_LEVELS; l++) { mn[l] = 0x7fffffff; mx[l] = -0x7fffffff - 1; }
@@ -190,43 +201,75 @@ KW_BODY void sn_wide_body(const KaiCtx& c, const SnArgs& a) {
         // ---- checkJobDomainFit :362-379 on the common domain, then the levels (job_filtering.go:84-100)
         auto dom_fits = [&](int d) { const int p = ap[d]; if (p != -1) return p >= tasks; return !(eng.job_ratio_fr(pq.sum.tr, fr + (size_t)d * KAI_MAX_RES) > 1.0); };
         int status = KAI_SUBSET_OK;
-        if (!dom_fits(domain)) status = KAI_SUBSET_NO_FIT;
+        const bool common_fits = dom_fits(domain);
+        if (!common_fits) status = KAI_SUBSET_NO_FIT;
         else if ((req < 0 && pref < 0) || req >= L || pref >= L) status = KAI_SUBSET_BAD_LEVEL;
+        // calculateNodeScores (job_filtering.go:87-90) runs behind the common domain's fit and in front of the level checks; rank: the preferred level is one of the topology's
+        const bool recorded = ws && common_fits && pref >= 0, rank = recorded && pref < L;
+        if (recorded && !rank && tid == 0) sn_score_row(a, i, KAI_TOPO_SCORES_EMPTY, 0);
+        const int max_depth = pref >= 0 ? pref : req;
+        // sortTreeFromRoot :447-486: every child's place among its siblings (the whole workgroup: two barriers)
+        auto sibling_places = [&] {
+            for (int d = tid; d < DT; d += lanes) if (c.dom_topo[d] == t) ratio[d] = eng.job_ratio_fr(pq.sum.tr, fr + (size_t)d * KAI_MAX_RES);
+            kw::sync();
+            for (int d = tid; d < DT; d += lanes) {
+                if (c.dom_topo[d] != t) continue;
+                if (d >= c.D) { place[d] = 0; continue; }
+                const int p = c.dom_parent[d], b0 = c.dom_child_off[p], b1 = c.dom_child_off[p + 1];
+                const bool sorted = eng.dom_in_subtree(p, domain) && !(dl <= max_depth && max_depth < c.dom_level[p]);
+                const double rx = ratio[d]; const uint32_t ix = c.dom_id_rank[d];
+                int r = 0; bool before = true;
+                for (int k = b0; k < b1; k++) {
+                    const int y = a.children[k];
+                    if (y == d) { before = false; continue; }
+                    if (sorted) { const double ry = ratio[y]; if (ry > rx || (ry == rx && c.dom_id_rank[y] < ix)) r++; }
+                    else if (before) r++;
+                }
+                place[d] = r;
+            }
+            kw::sync();
+        };
+        // every domain's path from the root as a number; where scores are ranked, the preferred-level domains of the common domain's sub-tree and their count (no barrier)
+        auto path_keys = [&] {
+            int scored = 0;
+            for (int d = tid; d < DT; d += lanes) {
+                if (rank) scd[d] = 0;
+                if (c.dom_topo[d] != t) continue;
+                int64_t k = 0, mul = 1;
+                for (int x = d, hops = 0; x >= 0 && c.dom_level[x] >= 0 && hops <= KAI_TOPO_SCAN_LEVELS; x = c.dom_parent[x], hops++) { k += (int64_t)place[x] * mul; mul *= DT; }
+                key[d] = k;
+                if (rank && d < c.D && c.dom_level[d] == pref && eng.dom_in_subtree(d, domain)) { scd[d] = 1; scored++; }
+            }
+            if (scored) kw::atomic_add(&s_nsc, scored);
+        };
+        // behind a barrier that follows path_keys: the i-th such domain in tree order (their parents lie above max_depth = pref: sorted sibling sets, so the paths order them
+        // as getLevelDomains' depth-first walk does) takes floor((i + 1) / n * 10)
+        auto store_deciles = [&] {
+            const int n = s_nsc;
+            for (int d = tid; d < c.D; d += lanes) {
+                if (!scd[d]) continue;
+                const int64_t k = key[d];
+                int idx = 0;
+                for (int e = 0; e < c.D; e++) if (scd[e] && key[e] < k) idx++;
+                drow[d] = sn_decile(idx, n);
+            }
+            if (tid == 0) sn_score_row(a, i, row0 + pref, n);
+        };
         if (status != KAI_SUBSET_OK) {  // (every lane read the same tables)
+            if (rank) { sibling_places(); path_keys(); kw::sync(); store_deciles(); }  // a bad REQUIRED level: the scores are recorded all the same
             if (tid == 0) sn_answer(a, i, status, 0, tasks, sn_domain_out(c, domain));
             kw::sync();
             continue;
         }
-        // ---- sortTreeFromRoot :447-486: every child's place among its siblings
-        const int max_depth = pref >= 0 ? pref : req;
-        for (int d = tid; d < DT; d += lanes) if (c.dom_topo[d] == t) ratio[d] = eng.job_ratio_fr(pq.sum.tr, fr + (size_t)d * KAI_MAX_RES);
-        kw::sync();
-        for (int d = tid; d < DT; d += lanes) {
-            if (c.dom_topo[d] != t) continue;
-            if (d >= c.D) { place[d] = 0; continue; }
-            const int p = c.dom_parent[d], b0 = c.dom_child_off[p], b1 = c.dom_child_off[p + 1];
-            const bool sorted = eng.dom_in_subtree(p, domain) && !(dl <= max_depth && max_depth < c.dom_level[p]);
-            const double rx = ratio[d]; const uint32_t ix = c.dom_id_rank[d];
-            int r = 0; bool before = true;
-            for (int k = b0; k < b1; k++) {
-                const int y = a.children[k];
-                if (y == d) { before = false; continue; }
-                if (sorted) { const double ry = ratio[y]; if (ry > rx || (ry == rx && c.dom_id_rank[y] < ix)) r++; }
-                else if (before) r++;
-            }
-            place[d] = r;
-        }
-        kw::sync();
+        sibling_places();
         // ---- getJobAllocatableDomains :265-310 over calculateRelevantDomainLevels :381-425, with every domain's path from the root as a number
+        path_keys();
         int mask = 0;
         {   bool fp = false, fq = false;
             for (int l = L - 1; l >= -1; l--) { if (l == pref && l >= 0) fp = true; if (l == req && l >= 0) fq = true; if (fp || fq) mask |= 1 << (l + 1); if (fq) break; } }
         int mine = 0;
         for (int d = tid; d < DT; d += lanes) {
             if (c.dom_topo[d] != t) { lvl[d] = -100; continue; }
-            int64_t k = 0, mul = 1;
-            for (int x = d, hops = 0; x >= 0 && c.dom_level[x] >= 0 && hops <= KAI_TOPO_SCAN_LEVELS; x = c.dom_parent[x], hops++) { k += (int64_t)place[x] * mul; mul *= DT; }
-            key[d] = k;
             const int l = c.dom_level[d];
             bool ch = (mask >> (l + 1)) & 1;
             if (ch && pq.restrict_active) {
@@ -241,6 +284,7 @@ KW_BODY void sn_wide_body(const KaiCtx& c, const SnArgs& a) {
         if (mine) kw::atomic_add(&s_cnt, mine);
         kw::sync();
         const int n_chosen = s_cnt;
+        if (rank) store_deciles();
         // ---- sortDomainInfos :526-542: deepest level first, level-order inside a level
         for (int d = tid; d < DT; d += lanes) {
             const int l = lvl[d];
@@ -275,6 +319,21 @@ KAI_HD void sn_engine_walk(const KaiCtx& c, Backend& be, const SnArgs& a) {
         if (n > a.stride) n = a.stride;
         for (int k = 0; k < n; k++) { const int d = a.etmp[k]; SnRaw o; o.domain = d; o.alloc_pods = d >= 0 ? c.dom_alloc_pods[d] : -1; a.raw[(size_t)i * a.stride + k] = o; }
         sn_answer(a, i, why.status, n, why.tasks, sn_domain_out(c, why.common));
+        if (a.want_scores) {  // slot 0 is the query's (n_keys started at 0): written exactly where the function recorded scores
+            KAI_GP(uint8_t) drow = a.deciles + (size_t)i * (size_t)c.D;
+            for (int d = 0; d < c.D; d++) drow[d] = KAI_TOPO_NO_SCORE;
+            int level_row = KAI_TOPO_SCORES_NONE, n_scored = 0;
+            if (be.local().n_keys > 0 && g.topo >= 0) {
+                const int L = c.topo_level_off[g.topo + 1] - c.topo_level_off[g.topo];
+                if (g.pref >= L) level_row = KAI_TOPO_SCORES_EMPTY;  // (the slot's row lies outside the topology: never handed on)
+                else {
+                    level_row = c.sg_row[0];
+                    KAI_GP(const double) sc = c.sg_score;
+                    for (int d = 0; d < c.D; d++) if (sc[d] >= 0) { drow[d] = (uint8_t)(sc[d] / 10000.0); n_scored++; }
+                }
+            }
+            sn_score_row(a, i, level_row, n_scored);
+        }
     }
     if (st.fault) { a.head->fault = st.fault; a.head->fault_line = st.fault_line; }
     st.fault = fault0; st.fault_line = line0;
@@ -338,8 +397,9 @@ KW_BODY void sn_emit_body(const KaiCtx& c, const SnArgs& a) {
 // Where the pieces of one call lie in the handle's scratch (device) and staging (pinned host), 16-byte aligned.  [perm | rank | children] is the session's part, sent with the first
 // call of a session; [queries | rows_in | head] is what every call sends, in ONE copy; [head | answers] is what comes back for the count, in one piece.
 struct SnLayout {
-    size_t perm, rank, children, tab_end, head, answers, count_end, queries, rows_in, up_end, rows, prep, raw, etmp, w_free, w_ratio, w_key, w_ap, w_place, w_lvl, end;
-    SnLayout(int N, int M, int S, int W, int stride, int DT, int n_children, int wgs) {
+    size_t perm, rank, children, tab_end, head, answers, count_end, queries, rows_in, up_end, rows, prep, raw, etmp, w_free, w_ratio, w_key, w_ap, w_place, w_lvl, w_sc, score_rows, deciles, end;
+    // scored (kai_subset_nodes_scored): [score_rows | deciles of D domains a query] in one piece and the flag table, behind everything kai_subset_nodes has
+    SnLayout(int N, int M, int S, int W, int stride, int DT, int n_children, int wgs, bool scored = false, int D = 0) {
         auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
         size_t o = 0;
         perm = o; o = al(o + (size_t)(N > 0 ? N : 1) * 4); rank = o; o = al(o + (size_t)(N > 0 ? N : 1) * 4); children = o; o = al(o + (size_t)(n_children > 0 ? n_children : 1) * 4); tab_end = o;
@@ -348,6 +408,8 @@ struct SnLayout {
         rows = o; o = al(o + (size_t)S * W * 4 + 4); prep = o; o = al(o + (size_t)M * sizeof(SnPrep)); raw = o; o = al(o + (size_t)M * stride * sizeof(SnRaw)); etmp = o; o = al(o + (size_t)stride * 4);
         const size_t dw = (size_t)(wgs > 0 ? wgs : 0) * (size_t)(DT > 0 ? DT : 1);
         w_free = o; o = al(o + dw * KAI_MAX_RES * 8); w_ratio = o; o = al(o + dw * 8); w_key = o; o = al(o + dw * 8); w_ap = o; o = al(o + dw * 4); w_place = o; o = al(o + dw * 4); w_lvl = o; o = al(o + dw * 4);
+        w_sc = o; o = al(o + (scored ? dw * 4 : 0));
+        score_rows = o; o = al(o + (scored ? (size_t)M * sizeof(kai_topo_score_row) : 0)); deciles = o; o = al(o + (scored ? (size_t)M * (size_t)(D > 0 ? D : 0) : 0));
         end = o;
     }
 };
@@ -356,7 +418,7 @@ inline SnArgs sn_bind_args(unsigned char* d, const SnLayout& L, int M, int S, in
     a.M = M; a.S = S; a.W = W; a.stride = stride;
 #define SN_B(field) a.field = (decltype(a.field))(d + L.field)
     SN_B(head); SN_B(queries); SN_B(rows_in); SN_B(perm); SN_B(rank); SN_B(children); SN_B(rows); SN_B(prep); SN_B(answers); SN_B(raw); SN_B(etmp);
-    SN_B(w_free); SN_B(w_ratio); SN_B(w_key); SN_B(w_ap); SN_B(w_place); SN_B(w_lvl);
+    SN_B(w_free); SN_B(w_ratio); SN_B(w_key); SN_B(w_ap); SN_B(w_place); SN_B(w_lvl); SN_B(w_sc); SN_B(score_rows); SN_B(deciles);
 #undef SN_B
     return a;
 }

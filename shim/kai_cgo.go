@@ -1081,6 +1081,144 @@ func SubsetNodes(jobs []*podgroup_info.PodGroupInfo) (sets [][][]*node_info.Node
 	return sets, status, true
 }
 
+// SubsetNodesScored: SubsetNodes with the topology plugin's node scores (calculateNodeScores, plugins/topology/node_scoring.go:37-53) in ONE kai_subset_nodes_scored call.
+// scores[i] is what OrderedNodesScored takes for the tasks of jobs[i]: the row of the job's root sub-group set — nil where the reference records none (no preferred level,
+// no constraint, a common domain that cannot take the gang): such a task is ordered without a topology term, or, for an inner sub-group asked through the C call, with the
+// nearest ancestor's row that is not KAI_TOPO_SCORES_NONE.  The scores are computed once per sub-group and NOT again between the tasks of a gang, as in the reference.
+// Not registered anywhere.  ok = false: as SubsetNodes.
+type TopologyScores struct {
+	row     C.kai_topo_score_row
+	deciles []C.uint8_t // [n_domains]: floor((idx + 1) / n * 10) per scored domain, KAI_TOPO_NO_SCORE elsewhere
+}
+
+func SubsetNodesScored(jobs []*podgroup_info.PodGroupInfo) (sets [][][]*node_info.NodeInfo, scores []*TopologyScores, status []int, ok bool) {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return nil, nil, nil, false
+	}
+	pack := current.pack
+	if len(jobs) == 0 {
+		return nil, nil, nil, true
+	}
+	jobOf := make(map[*podgroup_info.PodGroupInfo]int, len(pack.jobs))
+	for i, j := range pack.jobs {
+		jobOf[j] = i
+	}
+	queries := make([]C.kai_subset_query, len(jobs))
+	for i, j := range jobs {
+		idx, known := jobOf[j]
+		if !known {
+			return nil, nil, nil, false
+		}
+		queries[i] = C.kai_subset_query{job: C.int32_t(idx), group: -1, podset: -1, nodeset: -1}
+	}
+	words := (len(pack.nodes) + 31) / 32
+	domains := int(pack.soa.n_domains)
+	params := C.kai_subset_params{version: C.KAI_SUBSET_VERSION}
+	answers := make([]C.kai_subset_answer, len(jobs))
+	scoreRows := make([]C.kai_topo_score_row, len(jobs))
+	deciles := make([]C.uint8_t, len(jobs)*domains+1)
+	capSets := 8*len(jobs) + 64
+	var records []C.kai_node_set
+	var rows []C.uint32_t
+	var n C.int64_t
+	for try := 0; ; try++ {
+		records = make([]C.kai_node_set, capSets+1)
+		rows = make([]C.uint32_t, capSets*words+1)
+		// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+		rc := C.kai_subset_nodes_scored(core, &params, &queries[0], C.int32_t(len(queries)), nil, 0, &answers[0], &records[0], C.int64_t(capSets), &n, &rows[0], &scoreRows[0], &deciles[0], nil)
+		if rc == C.KAI_ERR_CAPACITY && try == 0 {
+			capSets = int(n) // decided before the first write: the arrays are as they were
+			continue
+		}
+		if rc != 0 {
+			return nil, nil, nil, false
+		}
+		break
+	}
+	sets = make([][][]*node_info.NodeInfo, len(jobs))
+	scores = make([]*TopologyScores, len(jobs))
+	status = make([]int, len(jobs))
+	for i, a := range answers {
+		status[i] = int(a.status)
+		sets[i] = make([][]*node_info.NodeInfo, int(a.n_sets))
+		for k := 0; k < int(a.n_sets); k++ {
+			r := int(a.first) + k
+			set := make([]*node_info.NodeInfo, 0, int(records[r].n_nodes))
+			for w := 0; w < words; w++ {
+				for bits := uint32(rows[r*words+w]); bits != 0; bits &= bits - 1 {
+					set = append(set, pack.nodes[w*32+mathbits.TrailingZeros32(bits)])
+				}
+			}
+			sets[i][k] = set
+		}
+		if scoreRows[i].level_row != C.KAI_TOPO_SCORES_NONE {
+			scores[i] = &TopologyScores{row: scoreRows[i], deciles: deciles[i*domains : (i+1)*domains : (i+1)*domains]}
+		}
+	}
+	return sets, scores, status, true
+}
+
+// OrderedNodesScored: OrderedNodes with the topology plugin's term (nodeOrderFn, plugins/topology/node_scoring.go:17-35) in ONE kai_ordered_nodes_scored call:
+// scores[i] (of SubsetNodesScored; nil = none) is the row task i is scored with — a node whose domain has no score in it is dropped from the list, the others get
+// decile x scores.Topology on top.  With k = 1 it is the scored BestNodes.  Not registered anywhere.  ok = false: as OrderedNodes, or len(scores) != len(tasks).
+func OrderedNodesScored(tasks []*pod_info.PodInfo, nodeSets [][]*node_info.NodeInfo, scores []*TopologyScores, pipelineOnly bool, k int) (nodes [][]*node_info.NodeInfo, isPipeline [][]bool, ok bool) {
+	if current == nil || current.pack == nil || current.pack.fallback || len(nodeSets) != len(tasks) || len(scores) != len(tasks) || k < 1 || k > C.KAI_ORDERED_MAX_K {
+		return nil, nil, false
+	}
+	pack := current.pack
+	if len(tasks) == 0 {
+		return nil, nil, true
+	}
+	plain, bitmaps, nRows, known := nodeQueries(pack, tasks, nodeSets, pipelineOnly)
+	if !known {
+		return nil, nil, false
+	}
+	domains := int(pack.soa.n_domains)
+	rowOf := map[*TopologyScores]int{} // tasks that share a TopologyScores share a row
+	var scoreRows []C.kai_topo_score_row
+	var deciles []C.uint8_t
+	queries := make([]C.kai_scored_query, len(tasks))
+	for i, q := range plain {
+		queries[i] = C.kai_scored_query{pod: q.pod, nodeset: q.nodeset, flags: q.flags, scores: -1}
+		sc := scores[i]
+		if sc == nil {
+			continue
+		}
+		row, seen := rowOf[sc]
+		if !seen {
+			if len(sc.deciles) != domains {
+				return nil, nil, false
+			}
+			row = len(scoreRows)
+			rowOf[sc] = row
+			scoreRows = append(scoreRows, sc.row)
+			deciles = append(deciles, sc.deciles...)
+		}
+		queries[i].scores = C.int32_t(row)
+	}
+	deciles = append(deciles, 0) // (never empty: &deciles[0] below)
+	scoreRows = append(scoreRows, C.kai_topo_score_row{level_row: C.KAI_TOPO_SCORES_NONE})
+	// cgo: the arrays hold no Go pointers, so they may be passed for the duration of the call
+	answers := make([]C.kai_node_answer, len(tasks)*k)
+	counts := make([]C.int32_t, len(tasks))
+	if rc := C.kai_ordered_nodes_scored(core, &queries[0], C.int32_t(len(queries)), ptr(bitmaps), C.int32_t(nRows), &scoreRows[0], &deciles[0], C.int32_t(len(scoreRows)-1), C.int32_t(k), &answers[0], &counts[0]); rc != 0 {
+		return nil, nil, false
+	}
+	nodes = make([][]*node_info.NodeInfo, len(tasks))
+	isPipeline = make([][]bool, len(tasks))
+	for i := range tasks {
+		n := int(counts[i])
+		nodes[i] = make([]*node_info.NodeInfo, n)
+		isPipeline[i] = make([]bool, n)
+		for j := 0; j < n; j++ {
+			a := answers[i*k+j]
+			nodes[i][j] = pack.nodes[a.node]
+			isPipeline[i][j] = a.is_pipeline != 0
+		}
+	}
+	return nodes, isPipeline, true
+}
+
 // replay: the committed operations through the real Statement.  kai_op.stmt numbers the Statements of the action in
 // commit order; one id = one Statement, e.g. a reclaim "evict A, evict B, pipeline C" (framework/statement.go:536-575).
 // An operation the live session refuses (the cache moved on since the snapshot, a bind conflict) discards its whole Statement —
