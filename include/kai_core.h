@@ -548,6 +548,56 @@ int kai_ordered_nodes(kai_core* core, const kai_node_query* queries, int32_t n_q
 typedef struct kai_apply_result { int64_t first_bad; int32_t path; int32_t statements; } kai_apply_result;
 int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_apply_result* result /* may be NULL */);
 
+/* ONE open (uncommitted) Statement on the handle: framework.Statement as the allocate loop uses it (framework/statement.go:44-61, 522-575; allocateSubGroupSet
+ * and attemptToAllocateJob in actions/common/allocate.go) — operations are applied WITHOUT the commit, logged on the device, rolled back to a checkpoint,
+ * discarded or committed.  With the query calls (kai_ordered_nodes*, kai_subset_nodes*) it is the allocate loop for the jobs a caller places itself: try a node
+ * set, roll back when the gang does not fit, try the next.
+ *  - kai_stmt_begin opens the Statement (version: KAI_STMT_VERSION).  KAI_ERR_STATE with one open already.  Every other kai_stmt_* call without an open
+ *    Statement: KAI_ERR_STATE.
+ *  - kai_stmt_apply applies ops[0 .. n_ops) in array order and appends them to the log.  The fields of kai_op are read as kai_ops_apply reads them: `node` is the
+ *    caller's index (for an evict: the node the pod is evicted from); `seq` and `job` are not read; `pad` must be 0; `stmt` is not read (there is one Statement).
+ *    KAI_OP_ALLOCATE is Statement.Allocate: the pod is left ALLOCATED, not Binding.  KAI_OP_PIPELINE is Statement.Pipeline(updateTaskIfExistsOnNode = true).
+ *    KAI_OP_EVICT is Statement.Evict and needs a pod on op.node.  The per-operation preconditions are kai_ops_apply's, against the state the Statement has
+ *    reached.  A failing precondition: KAI_ERR_STATE, result->first_bad is the operation, nothing is written, the Statement stays open with its log as it was.
+ *    The log has room for n_pods * 2 + 32 operations (half of the device log: the engine's rollback pushes one undo record per undone operation on top of the
+ *    log before it truncates, so a discard of L records needs 2 L of them); a call that would exceed it: KAI_ERR_CAPACITY, nothing is written.
+ *    KAI_APPLY_CHECK_ONLY validates and writes nothing.  n_ops == 0: KAI_OK without a device call.
+ *  - kai_stmt_checkpoint: *cp_out = the log's length.  Host only: no device call.
+ *  - kai_stmt_rollback(cp) undoes the operations [cp, log_len), last first as Statement.Rollback does.  Afterwards the handle is indistinguishable from a twin on
+ *    which kai_stmt_begin and only the first cp operations were applied: kai_pod_states, kai_node_states and kai_queue_shares bit for bit, the answers of
+ *    kai_best_node(s), kai_ordered_nodes*, kai_subset_nodes* and kai_job_order, and everything after a later commit — the operations and kai_action_stats of
+ *    the next actions included (rolled-back evictions and pipelines do not keep the allocate action off its batch path).  cp outside 0 .. log_len:
+ *    KAI_ERR_INVALID_ARG.  cp == log_len: KAI_OK without a launch.
+ *  - kai_stmt_discard is kai_stmt_rollback(0), then the Statement is closed.  In a session whose quantities add exactly (whole GPUs, integral milli-CPU and
+ *    memory: what the batch path of the allocate action asks for) the three read-backs afterwards equal those before kai_stmt_begin bit for bit.
+ *  - kai_stmt_commit commits as Statement.Commit does (an allocated pod becomes Binding) and closes the Statement.  Afterwards the handle is indistinguishable
+ *    from one on which kai_ops_apply took the surviving operations as one Statement.  ops_out (may be NULL) gets them as kai_op: seq from 0, stmt 0, job filled,
+ *    nodes in the caller's indices; *n_ops (may be NULL) their number.  ops_cap below it: KAI_ERR_CAPACITY with *n_ops set, the Statement stays open and
+ *    uncommitted.
+ * While a Statement is open: every query call and the three read-backs work, see the tentative state and leave the log untouched.  kai_action_execute,
+ * kai_ops_apply and kai_stale_gang_eviction return KAI_ERR_STATE and write nothing.  kai_session_open, kai_session_reset, kai_session_update* and
+ * kai_session_close drop the Statement with everything else they drop.
+ * Other refusals, as kai_ops_apply's: KAI_ERR_UNSUPPORTED for a handle of a sharded group (n_gpus > 1) and for a session with shared-GPU requests;
+ * KAI_ERR_INVALID_ARG for a wrong version, NULL ops with n_ops > 0, a negative count, unknown flags bits (kai_stmt_apply: KAI_APPLY_CHECK_ONLY,
+ * KAI_APPLY_ENGINE_PATH; rollback and discard: KAI_APPLY_ENGINE_PATH), a kind outside 0..2, a pod or node index out of range, non-zero pad, a NULL cp_out, a
+ * negative ops_cap or NULL ops_out with ops_cap > 0.  Every refusal is decided before the first write.  KAI_ERR_DEVICE_FAULT (the engine's own state disagrees
+ * with the pod states) and any other failure behind the first launch (KAI_ERR_HIP, KAI_ERR_NO_MEMORY) close the Statement; kai_session_reset is the way on.
+ * result (may be NULL): first_bad as in kai_apply_result; log_len the log's length after the call (0 after discard and commit); path (KAI_APPLY_PATH_*) the
+ * path that took the call.  Two paths over one log (kai_stmt.hpp; the engine's own Statement records, so either path takes over at any point): chip-wide
+ * kernels where every pod is named at most once in the surviving log plus the batch and every operation starts from a state kai_ops_apply's chip-wide path
+ * takes — apply: one upload, two launches; rollback, discard, commit: one launch; each one small download and one synchronise — and one lane through the
+ * engine's own Statement functions for everything else (KAI_APPLY_ENGINE_PATH: also where the chip-wide path qualifies).
+ * Not covered: Pipeline with updateTaskIfExistsOnNode = false and Statement.Unevict; ConvertAllAllocatedToPipelined (roll back and pipeline instead); several
+ * open Statements. */
+#define KAI_STMT_VERSION 1u
+typedef struct kai_stmt_result { int64_t first_bad; int64_t log_len; int32_t path; int32_t pad; } kai_stmt_result;
+int kai_stmt_begin(kai_core* core, uint32_t version);
+int kai_stmt_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_stmt_result* result /* may be NULL */);
+int kai_stmt_checkpoint(kai_core* core, int64_t* cp_out);
+int kai_stmt_rollback(kai_core* core, int64_t cp, uint32_t flags, kai_stmt_result* result /* may be NULL */);
+int kai_stmt_discard(kai_core* core, uint32_t flags, kai_stmt_result* result /* may be NULL */);
+int kai_stmt_commit(kai_core* core, kai_op* ops_out /* may be NULL */, int64_t ops_cap, int64_t* n_ops /* may be NULL */, kai_stmt_result* result /* may be NULL */);
+
 /* replaces: the stalegangeviction action (actions/stalegangeviction/stalegangeviction.go:29-90), the fifth of the default action list.  The decision is taken on
  * the device against the session's CURRENT state (after whatever actions or kai_ops_apply calls ran) and the evictions are applied as kai_ops_apply applies
  * KAI_OP_EVICT operations (ssn.Evict, framework/session.go:127-150).

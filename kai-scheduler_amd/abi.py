@@ -237,6 +237,14 @@ class KaiApplyResult(C.Structure):
     _fields_ = [("first_bad", C.c_int64), ("path", C.c_int32), ("statements", C.c_int32)]
 
 
+STMT_VERSION = 1  # KAI_STMT_VERSION
+
+
+class KaiStmtResult(C.Structure):
+    """kai_stmt_result (include/kai_core.h): what a kai_stmt_* call says — the first offending operation (-1 = none), the log's length after the call, the path that took it."""
+    _fields_ = [("first_bad", C.c_int64), ("log_len", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
+
+
 STALE_VERSION, STALE_DRY_RUN = 1, 0x1  # KAI_STALE_VERSION, KAI_STALE_DRY_RUN
 
 

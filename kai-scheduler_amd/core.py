@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes", "kai_subset_nodes_scored", "kai_ordered_nodes_scored",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stmt_begin", "kai_stmt_apply", "kai_stmt_checkpoint", "kai_stmt_rollback", "kai_stmt_discard", "kai_stmt_commit", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes", "kai_subset_nodes_scored", "kai_ordered_nodes_scored",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -127,6 +127,12 @@ def load_library(path: str = LIB_PATH):
     lib.kai_best_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiNodeAnswer)]
     lib.kai_ordered_nodes.argtypes = [C.c_void_p, C.POINTER(abi.KaiNodeQuery), C.c_int32, C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(abi.KaiNodeAnswer), C.POINTER(C.c_int32)]
     lib.kai_ops_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiApplyResult)]
+    lib.kai_stmt_begin.argtypes = [C.c_void_p, C.c_uint32]
+    lib.kai_stmt_apply.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.c_uint32, C.POINTER(abi.KaiStmtResult)]
+    lib.kai_stmt_checkpoint.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.kai_stmt_rollback.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(abi.KaiStmtResult)]
+    lib.kai_stmt_discard.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.KaiStmtResult)]
+    lib.kai_stmt_commit.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64), C.POINTER(abi.KaiStmtResult)]
     lib.kai_stale_gang_eviction.argtypes = [C.c_void_p, C.POINTER(abi.KaiStaleParams), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(abi.KaiOp), C.c_int64,
                                             C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
     lib.kai_job_order.argtypes = [C.c_void_p, C.POINTER(abi.KaiJobOrderParams), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -392,6 +398,11 @@ class Session:
             raise err
         return res
 
+    def statement(self) -> "Statement":
+        """kai_stmt_begin: the session's one open (uncommitted) Statement — apply / checkpoint / rollback / discard / commit.  As a context manager it discards on an
+        exception and on leaving the block uncommitted."""
+        return Statement(self)
+
     def stale_gang_eviction(self, stale_since, grace_ns: int, dry_run: bool = False):
         """kai_stale_gang_eviction: the stalegangeviction action against the session's current state, at the handle's clock (KaiCore.set_now).  stale_since: per job
         StalenessInfo.TimeStamp in ns, 0 = nil (not modified); grace_ns < 0: never evict; dry_run: decide and report, the session is not written.
@@ -537,3 +548,70 @@ class Session:
 
     def close(self):
         self.core.lib.kai_session_close(self.core.handle)
+
+
+class Statement:
+    """An open Statement on a session (kai_stmt_*, include/kai_core.h): operations applied without the commit, logged on the device, rolled back to a checkpoint,
+    discarded or committed.  While it is open the session's queries and read-backs see the tentative state; actions, apply_ops and stale_gang_eviction are refused."""
+
+    def __init__(self, ssn: Session):
+        self.ssn, self.core, self.open = ssn, ssn.core, False
+        self.core._check(self.core.lib.kai_stmt_begin(self.core.handle, abi.STMT_VERSION))
+        self.open = True
+
+    def _done(self, rc, res):
+        if rc != 0:
+            err = KaiError(rc, self.core.lib.kai_last_error(self.core.handle).decode())
+            err.result = res
+            raise err
+        return res
+
+    def apply(self, ops, check_only: bool = False, engine_path: bool = False):
+        """kai_stmt_apply: `ops` as apply_ops takes them (stmt is not read); an allocated pod is left Allocated.  Returns the kai_stmt_result; a refusal raises KaiError
+        with the result as its `.result` and leaves the Statement open as it was."""
+        arr = np.ascontiguousarray(ops, dtype=_OP_DTYPE)
+        res = abi.KaiStmtResult()
+        flags = (abi.APPLY_CHECK_ONLY if check_only else 0) | (abi.APPLY_ENGINE_PATH if engine_path else 0)
+        return self._done(self.core.lib.kai_stmt_apply(self.core.handle, arr.ctypes.data_as(C.POINTER(abi.KaiOp)) if len(arr) else None, len(arr), flags, C.byref(res)), res)
+
+    def checkpoint(self) -> int:
+        """kai_stmt_checkpoint: the log's length (no device call)."""
+        cp = C.c_int64(0)
+        self.core._check(self.core.lib.kai_stmt_checkpoint(self.core.handle, C.byref(cp)))
+        return cp.value
+
+    def rollback(self, cp: int, engine_path: bool = False):
+        """kai_stmt_rollback: the operations behind checkpoint `cp` undone.  Returns the kai_stmt_result."""
+        res = abi.KaiStmtResult()
+        return self._done(self.core.lib.kai_stmt_rollback(self.core.handle, int(cp), abi.APPLY_ENGINE_PATH if engine_path else 0, C.byref(res)), res)
+
+    def discard(self, engine_path: bool = False):
+        """kai_stmt_discard: every operation undone, the Statement closed.  Returns the kai_stmt_result."""
+        res = abi.KaiStmtResult()
+        rc = self.core.lib.kai_stmt_discard(self.core.handle, abi.APPLY_ENGINE_PATH if engine_path else 0, C.byref(res))
+        self.open = self.open and rc != 0
+        return self._done(rc, res)
+
+    def commit(self):
+        """kai_stmt_commit: the surviving operations committed (allocated pods become Binding), the Statement closed.  Returns (ops, result): the operations as
+        kai_op records — seq from 0, stmt 0, job filled, nodes in the caller's indices."""
+        cap = self.checkpoint()
+        ops = np.zeros(max(cap, 1), _OP_DTYPE)
+        n, res = C.c_int64(0), abi.KaiStmtResult()
+        rc = self.core.lib.kai_stmt_commit(self.core.handle, ops.ctypes.data_as(C.POINTER(abi.KaiOp)), cap, C.byref(n), C.byref(res))
+        self.open = self.open and rc != 0
+        self._done(rc, res)
+        return ops[:n.value].copy(), res
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.open:
+            try:
+                self.discard()
+            except KaiError:
+                if exc_type is None:
+                    raise
+                self.open = False  # (the session went with what raised: nothing is left to discard)
+        return False

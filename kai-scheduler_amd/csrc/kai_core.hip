@@ -121,6 +121,7 @@ int kai_action_execute(kai_core* core, int action, kai_op* ops_out, int64_t ops_
     if (!core || !n_ops) return KAI_ERR_INVALID_ARG;
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
     if (action < KAI_ACTION_ALLOCATE || action > KAI_ACTION_PREEMPT) return fail(core, KAI_ERR_INVALID_ARG, "unknown action");
+    if (core->st_open) return fail(core, KAI_ERR_STATE, "kai_action_execute: a Statement is open (kai_stmt_commit or kai_stmt_discard first)");
     if (action != KAI_ACTION_ALLOCATE && core->cfg.use_scheduling_signatures && !core->ctx.j_signature && core->ctx.J > 0) return fail(core, KAI_ERR_UNSUPPORTED, "use_scheduling_signatures needs kai_snapshot_soa.job_signature (actions/common/minimal_job_comparison.go)");
     HIP_TRY(core, hipSetDevice(core->device));
     return action_execute(core, action, ops_out, ops_cap, n_ops);
@@ -345,6 +346,7 @@ int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t fla
     if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_ops_apply: a handle of a sharded group");
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
     if (core->shared) return fail(core, KAI_ERR_UNSUPPORTED, "kai_ops_apply: a session with shared-GPU requests (kai_op carries no GPU group)");
+    if (core->st_open) return fail(core, KAI_ERR_STATE, "kai_ops_apply: a Statement is open (kai_stmt_commit or kai_stmt_discard first)");
     if (n_ops == 0) return KAI_OK;
     if (n_ops > (int64_t)0x7fffffff - 16) return fail(core, KAI_ERR_CAPACITY, "kai_ops_apply: more than 2^31 - 16 operations");
     KaiCtx& c = core->ctx;
@@ -399,6 +401,204 @@ int kai_ops_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t fla
     return KAI_OK;
 }
 
+// kai_stmt_*'s kernels for st_apply_drive / st_range_drive (kai_stmt.hpp), on top of the apply's launcher (the check kernel and the verdict's download are kai_ops_apply's)
+struct StLauncher : OaLauncher {
+    static dim3 g(int n) { return dim3((unsigned)n); }
+    void apply(int n, int b, const KaiCtx& c, const StArgs& s) { hipLaunchKernelGGL(k_st_apply, g(n), g(b), 0, core->stream, c, s); }
+    void undo(int n, int b, const KaiCtx& c, const StArgs& s) { hipLaunchKernelGGL(k_st_undo, g(n), g(b), 0, core->stream, c, s); }
+    void commit(int n, int b, const KaiCtx& c, const StArgs& s) { hipLaunchKernelGGL(k_st_commit, g(n), g(b), 0, core->stream, c, s); }
+    int engine(const KaiCtx&, const StArgs& s) {
+        if (!(s.a.flags & KAI_APPLY_CHECK_ONLY)) { const int rcs = solver_ensure(core); if (rcs) return rcs; }  // (binds core->ctx.sv: the context is read after it)
+        hipLaunchKernelGGL(k_st_engine, dim3(1), dim3(64), 0, core->stream, core->ctx, s);
+        return KAI_OK;
+    }
+};
+enum : uint8_t { ST_REC_KIND = 3, ST_REC_WIDE = 4 };  // kai_core::st_rec
+
+// what every kai_stmt_* call refuses before anything else; open_wanted: the call needs an open Statement (begin: none)
+static int st_entry(kai_core* core, const char* what, bool open_wanted, kai_stmt_result* result) {
+    if (result) { result->first_bad = -1; result->log_len = core && core->st_open ? (int64_t)core->st_rec.size() : 0; result->path = KAI_APPLY_PATH_NONE; result->pad = 0; }
+    if (!core) return KAI_ERR_INVALID_ARG;
+    auto say = [&](int code, const char* why) { core->err = std::string(what) + ": " + why; return code; };
+    if (core->world > 1) return say(KAI_ERR_UNSUPPORTED, "a handle of a sharded group");
+    if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
+    if (core->shared) return say(KAI_ERR_UNSUPPORTED, "a session with shared-GPU requests (kai_op carries no GPU group)");
+    if (open_wanted && !core->st_open) return say(KAI_ERR_STATE, "no open Statement (kai_stmt_begin)");
+    if (!open_wanted && core->st_open) return say(KAI_ERR_STATE, "a Statement is open already");
+    return KAI_OK;
+}
+// the arguments every call's kernels share: the Statement's stamps and verdict, the log as the host counts it
+static StArgs st_args(kai_core* core, int mode) {
+    const StLayout L(core->st_pod_cap); unsigned char* d = core->st_dev.p;
+    StArgs s{};
+    s.a.flags = oa_wide_session(core->ctx) ? 0u : KAI_OA_NOT_WIDE; s.a.use_islot = oa_use_islot(core->ctx);
+    s.a.head = (KAI_GP(OaHead))(d + L.head); s.a.stamp = (KAI_GP(int32_t))(d + L.stamp);
+    s.len = (int32_t)core->st_rec.size(); s.mode = mode;
+    return s;
+}
+static int st_device_fault(kai_core* core, const char* what, const OaHead& hv) {
+    char buf[200]; std::snprintf(buf, sizeof buf, "%s: device engine fault code %d (engine source line %d), path reported %d; the Statement is closed", what, hv.fault, hv.fault_line, hv.applied);
+    core->err = buf; core->st_open = false; return KAI_ERR_DEVICE_FAULT;
+}
+// any other failure behind the first launch (a HIP error, the solver scratch): the stamps and the log on the device may no longer be what the host counted — the Statement
+// is closed, the call's own status and message stay
+static int st_lost(kai_core* core, int rc) { core->st_open = false; core->err += "; the Statement is closed"; return rc; }
+
+int kai_stmt_begin(kai_core* core, uint32_t version) {
+    KAI_TRY(st_entry(core, "kai_stmt_begin", false, nullptr));
+    if (version != KAI_STMT_VERSION) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_begin: wrong version");
+    KaiCtx& c = core->ctx;
+    HIP_TRY(core, hipSetDevice(core->device));
+    // the Statement's own memory: the stamps of this session's pods and the verdict.  Grows here and nowhere else
+    const size_t P = (size_t)c.P, room = (size_t)st_log_room(c);
+    if (P > core->st_pod_cap || !core->st_dev.p) {
+        const size_t pod_cap = std::max(std::max<size_t>(P + P / 4, 1024), core->st_pod_cap);
+        KAI_TRY(reserve(core, core->st_dev, SIZE_MAX, StLayout(pod_cap).end));
+        core->st_pod_cap = pod_cap;
+    }
+    const StLayout L(core->st_pod_cap);
+    KAI_TRY(reserve(core, core->st_pin, 2 * sizeof(OaHead), (size_t)1 << 16));  // [the verdict up | the verdict down | the committed operations: grown by the commit]
+    HIP_TRY(core, hipMemsetAsync(core->st_dev.p + L.stamp, 0, std::max<size_t>(P, 1) * 4, core->stream));  // no pod is named yet
+    HIP_TRY(core, hipMemsetAsync(KAI_VP(c.st), 0, 2 * sizeof(int32_t), core->stream));                      // EngineState::ops_len, n_undo: the log is empty
+    static_assert(offsetof(EngineState, ops_len) == 0 && offsetof(EngineState, n_undo) == 4, "the log's length and its undo count lead EngineState");
+    core->st_rec.clear(); core->st_rec.reserve(room);
+    core->st_open = true;
+    return KAI_OK;
+}
+
+int kai_stmt_apply(kai_core* core, const kai_op* ops, int64_t n_ops, uint32_t flags, kai_stmt_result* result) {
+    // every host-decidable refusal before the first device call; `result` always leaves with a defined content
+    KAI_TRY(st_entry(core, "kai_stmt_apply", true, result));
+    if (n_ops < 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_apply: a negative count");
+    if (flags & ~(KAI_APPLY_CHECK_ONLY | KAI_APPLY_ENGINE_PATH)) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_apply: unknown flag bits");
+    if (n_ops > 0 && !ops) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_apply: ops is NULL");
+    if (n_ops == 0) return KAI_OK;
+    KaiCtx& c = core->ctx;
+    const int N = c.N, P = c.P;
+    const int64_t len = (int64_t)core->st_rec.size();
+    if (len + n_ops > (int64_t)st_log_room(c)) return fail(core, KAI_ERR_CAPACITY, "kai_stmt_apply: the log would exceed its room (ops_cap / 2 = 2 n_pods + 32 records: a rollback pushes one undo record per undone operation)");
+    const int n = (int)n_ops;
+    for (int i = 0; i < n; i++) {  // O(n): what no device is needed for
+        const kai_op& o = ops[i];
+        const char* why = nullptr;
+        if (o.kind < KAI_OP_ALLOCATE || o.kind > KAI_OP_EVICT) why = "kai_stmt_apply: kind outside 0..2";
+        else if (o.pod < 0 || o.pod >= P) why = "kai_stmt_apply: pod index out of range";
+        else if (o.node < 0 || o.node >= N) why = "kai_stmt_apply: node index out of range";
+        else if (o.pad != 0) why = "kai_stmt_apply: pad is not zero";
+        if (why) { if (result) result->first_bad = i; return fail(core, KAI_ERR_INVALID_ARG, why); }
+    }
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- kai_ops_apply's scratch and staging for the batch and the shadow (the stamps are the Statement's own: a growth here loses nothing)
+    KAI_TRY(oa_reserve_scratch(core, n));
+    const OaLayout L(core->oa_pod_cap, n);
+    const size_t up_bytes = L.end - L.head, pin_need = up_bytes + sizeof(OaHead);  // [head | ops][the verdict]
+    KAI_TRY(reserve(core, core->oa_pin, pin_need, std::max<size_t>(pin_need + pin_need / 2, (size_t)1 << 16)));
+    if (!core->oa_rank_ok) { core->oa_rank.assign((size_t)std::max(N, 1), 0); for (int i = 0; i < N; i++) core->oa_rank[(size_t)core->perm[i]] = i; core->oa_rank_ok = true; }
+    // ---- one staging upload: [head | ops], the nodes as name ranks
+    unsigned char* h = core->oa_pin.p; unsigned char* d = core->oa_dev.p;
+    OaHead* hh = reinterpret_cast<OaHead*>(h); std::memset(hh, 0, sizeof(OaHead)); hh->bad = KAI_OA_NONE;
+    {   kai_op* dst = reinterpret_cast<kai_op*>(h + sizeof(OaHead)); const int32_t* rank = core->oa_rank.data();
+        parallel_chunks((size_t)n, [&](int, size_t i0, size_t i1) { for (size_t i = i0; i < i1; i++) { kai_op o = ops[i]; o.node = rank[o.node]; dst[i] = o; } }); }
+    HIP_TRY(core, hipMemcpyAsync(d + L.head, h, up_bytes, hipMemcpyHostToDevice, core->stream));
+    StArgs s = st_args(core, KAI_ST_APPLY);
+    s.a.n = n; s.a.flags |= flags;
+    s.a.ops = (KAI_GP(const kai_op))(d + L.ops); s.a.head = (KAI_GP(OaHead))(d + L.head);
+    s.a.sh_status = (KAI_GP(int32_t))(d + L.sh_status); s.a.sh_node = (KAI_GP(int32_t))(d + L.sh_node);
+    // ---- the check and the chip-wide apply, one small download, one synchronise; the engine walk and a second download where the batch needs it
+    StLauncher launcher{{core, h + up_bytes}};
+    OaHead hv{}; int path = KAI_APPLY_PATH_NONE;
+    const int rcd = st_apply_drive(launcher, core->ctx, s, KAI_OA_WG, hv, path);
+    if (rcd == KAI_ERR_STATE) {
+        if (result) result->first_bad = hv.bad;
+        return fail(core, KAI_ERR_STATE, "kai_stmt_apply: an operation's precondition fails (ALLOCATE: a Pending pod; PIPELINE: Pending or Releasing; EVICT: a pod on op.node)");
+    }
+    if (rcd == KAI_ERR_DEVICE_FAULT) return st_device_fault(core, "kai_stmt_apply", hv);
+    if (rcd) return st_lost(core, rcd);
+    if (!(flags & KAI_APPLY_CHECK_ONLY)) {
+        const uint8_t wide = path == KAI_APPLY_PATH_WIDE ? ST_REC_WIDE : 0;
+        for (int i = 0; i < n; i++) core->st_rec.push_back((uint8_t)ops[i].kind | wide);
+        core->index_stale = true;  // neither path keeps the class index: rebuilt before the next action reads it
+    }
+    if (result) { result->path = path; result->log_len = (int64_t)core->st_rec.size(); }
+    return KAI_OK;
+}
+
+int kai_stmt_checkpoint(kai_core* core, int64_t* cp_out) {
+    KAI_TRY(st_entry(core, "kai_stmt_checkpoint", true, nullptr));
+    if (!cp_out) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_checkpoint: cp_out is NULL");
+    *cp_out = (int64_t)core->st_rec.size();
+    return KAI_OK;
+}
+
+// rollback (close = false) and discard (cp = 0, close = true): the records [cp, len) undone, chip-wide where the host knows every one of them `wide`
+static int st_rollback(kai_core* core, const char* what, int64_t cp, uint32_t flags, bool close, kai_stmt_result* result) {
+    KAI_TRY(st_entry(core, what, true, result));
+    auto say = [&](int code, const char* why) { core->err = std::string(what) + ": " + why; return code; };
+    if (flags & ~KAI_APPLY_ENGINE_PATH) return say(KAI_ERR_INVALID_ARG, "unknown flag bits");
+    const int64_t len = (int64_t)core->st_rec.size();
+    if (cp < 0 || cp > len) return say(KAI_ERR_INVALID_ARG, "cp outside 0 .. log_len");
+    if (cp == len) { if (close) core->st_open = false; if (result && close) result->log_len = 0; return KAI_OK; }  // nothing to undo: no launch
+    bool wide = !(flags & KAI_APPLY_ENGINE_PATH) && oa_wide_session(core->ctx);
+    for (int64_t i = cp; i < len && wide; i++) wide = (core->st_rec[(size_t)i] & ST_REC_WIDE) != 0;
+    HIP_TRY(core, hipSetDevice(core->device));
+    StArgs s = st_args(core, close ? KAI_ST_DISCARD : KAI_ST_ROLLBACK);
+    s.cp = (int32_t)cp;
+    unsigned char* h = core->st_pin.p;
+    OaHead* hh = reinterpret_cast<OaHead*>(h); std::memset(hh, 0, sizeof(OaHead)); hh->bad = KAI_OA_NONE;
+    HIP_TRY(core, hipMemcpyAsync((void*)s.a.head, h, sizeof(OaHead), hipMemcpyHostToDevice, core->stream));
+    StLauncher launcher{{core, h + sizeof(OaHead)}};
+    OaHead hv{}; int path = KAI_APPLY_PATH_NONE;
+    const int rcd = st_range_drive(launcher, core->ctx, s, KAI_OA_WG, wide, hv, path);
+    if (rcd == KAI_ERR_DEVICE_FAULT) return st_device_fault(core, what, hv);
+    if (rcd) return st_lost(core, rcd);
+    core->st_rec.resize((size_t)cp);
+    core->index_stale = true;
+    if (close) core->st_open = false;
+    if (result) { result->path = path; result->log_len = cp; }
+    return KAI_OK;
+}
+int kai_stmt_rollback(kai_core* core, int64_t cp, uint32_t flags, kai_stmt_result* result) { return st_rollback(core, "kai_stmt_rollback", cp, flags, false, result); }
+int kai_stmt_discard(kai_core* core, uint32_t flags, kai_stmt_result* result) { return st_rollback(core, "kai_stmt_discard", 0, flags, true, result); }
+
+int kai_stmt_commit(kai_core* core, kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, kai_stmt_result* result) {
+    KAI_TRY(st_entry(core, "kai_stmt_commit", true, result));
+    if (ops_cap < 0 || (ops_cap > 0 && !ops_out)) return fail(core, KAI_ERR_INVALID_ARG, "kai_stmt_commit: a negative capacity, or ops_out is NULL");
+    const int64_t len = (int64_t)core->st_rec.size();
+    if (ops_out && ops_cap < len) { if (n_ops) *n_ops = len; return fail(core, KAI_ERR_CAPACITY, "kai_stmt_commit: ops_cap is below the number of surviving operations (*n_ops holds it)"); }
+    if (n_ops) *n_ops = len;
+    if (len == 0) { core->st_open = false; if (result) result->log_len = 0; return KAI_OK; }  // nothing survived: no launch
+    KaiCtx& c = core->ctx;
+    bool wide = oa_wide_session(c), non_alloc = false;
+    for (uint8_t r : core->st_rec) { if (!(r & ST_REC_WIDE)) wide = false; if ((r & ST_REC_KIND) != KAI_OP_ALLOCATE) non_alloc = true; }
+    HIP_TRY(core, hipSetDevice(core->device));
+    // the committed operations: a device buffer and, where the caller wants them, pinned staging; grow on demand, no allocation once the handle is warm
+    const size_t out_bytes = (size_t)len * sizeof(kai_op), pin_need = 2 * sizeof(OaHead) + (ops_out ? out_bytes : 0);
+    KAI_TRY(reserve(core, core->st_out, out_bytes, out_bytes + out_bytes / 2 + 1024 * sizeof(kai_op)));
+    KAI_TRY(reserve(core, core->st_pin, pin_need, pin_need + pin_need / 2));
+    StArgs s = st_args(core, KAI_ST_COMMIT);
+    s.out = (KAI_GP(kai_op))core->st_out.p; s.out_cap = len;
+    unsigned char* h = core->st_pin.p;
+    OaHead* hh = reinterpret_cast<OaHead*>(h); std::memset(hh, 0, sizeof(OaHead)); hh->bad = KAI_OA_NONE;
+    HIP_TRY(core, hipMemcpyAsync((void*)s.a.head, h, sizeof(OaHead), hipMemcpyHostToDevice, core->stream));
+    StLauncher launcher{{core, h + sizeof(OaHead)}};
+    unsigned char* h_ops = h + 2 * sizeof(OaHead);
+    OaHead hv{}; int path = KAI_APPLY_PATH_NONE;
+    // (the operations ride in front of the verdict on the same stream: read_head's synchronise covers both)
+    struct WithOps : StLauncher { unsigned char* h_ops; const StArgs* s; size_t bytes; bool want;
+        int read_head(OaHead& hv_, const OaArgs& a) { if (want) HIP_TRY(core, hipMemcpyAsync(h_ops, (const void*)s->out, bytes, hipMemcpyDeviceToHost, core->stream)); return StLauncher::read_head(hv_, a); } };
+    WithOps wl{launcher, h_ops, &s, (size_t)len * sizeof(kai_op), ops_out != nullptr};
+    const int rcd = st_range_drive(wl, core->ctx, s, KAI_OA_WG, wide, hv, path);
+    if (rcd == KAI_ERR_DEVICE_FAULT) return st_device_fault(core, "kai_stmt_commit", hv);
+    if (rcd) return st_lost(core, rcd);
+    if (ops_out) { const kai_op* src = reinterpret_cast<const kai_op*>(h_ops); const int32_t* perm = core->perm.data();  // name rank -> the caller's node index
+        parallel_chunks((size_t)len, [&](int, size_t i0, size_t i1) { for (size_t i = i0; i < i1; i++) { kai_op o = src[i]; o.node = perm[o.node]; ops_out[i] = o; } }); }
+    core->index_stale = true;
+    if (non_alloc) c.fast_ok = 0;  // something is releasing / pipelined in the session from here on, as after kai_ops_apply of such operations
+    core->st_rec.clear(); core->st_open = false;
+    if (result) { result->path = path; result->log_len = 0; }
+    return KAI_OK;
+}
+
 // kai_stale_gang_eviction's kernels for sg_drive (kai_stale_gangs.hpp), on top of the apply's launcher; pin: [the counts | the apply's verdict] in the handle's staging
 struct SgLauncher : OaLauncher {
     unsigned char* pin_counts;
@@ -438,6 +638,7 @@ int kai_stale_gang_eviction(kai_core* core, const kai_stale_params* params, int6
     if (core->world > 1) return fail(core, KAI_ERR_UNSUPPORTED, "kai_stale_gang_eviction: a handle of a sharded group");
     if (!core->open) return fail(core, KAI_ERR_STATE, "no open session");
     if (core->shared) return fail(core, KAI_ERR_UNSUPPORTED, "kai_stale_gang_eviction: a session with shared-GPU requests (kai_op carries no GPU group)");
+    if (core->st_open) return fail(core, KAI_ERR_STATE, "kai_stale_gang_eviction: a Statement is open (kai_stmt_commit or kai_stmt_discard first)");
     KaiCtx& c = core->ctx;
     if (c.now_ns <= 0) return fail(core, KAI_ERR_INVALID_ARG, "kai_stale_gang_eviction: the handle's clock is not above 0 (kai_core_set_now): 0 stands for no timestamp");
     const int J = c.J, P = c.P;

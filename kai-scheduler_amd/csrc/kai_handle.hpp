@@ -25,6 +25,7 @@
 #include "kai_best_nodes.hpp"
 #include "kai_ordered_nodes.hpp"
 #include "kai_ops_apply.hpp"
+#include "kai_stmt.hpp"
 #include "kai_stale_gangs.hpp"
 #include "kai_job_order.hpp"
 #include "kai_subset_nodes.hpp"
@@ -115,7 +116,11 @@ struct kai_core {
     // kai_subset_nodes (kai_subset_nodes.hpp): pinned staging, device scratch and the emitted sets' own buffer, grow, live with the handle; whether the scratch holds this session's
     // tables (both node permutations, the open's children table); the session's topologies: raw records a query can have, the most levels of one (found with the first call)
     HandleBuf sn_pin{true}, sn_dev{false}, sn_out{false}; bool sn_tab_ok = false, sn_shape_ok = false; int sn_stride = 1, sn_levels = 0;
-    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &sn_pin, &sn_dev, &sn_out, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
+    // kai_stmt_* (kai_stmt.hpp): the open Statement — the log's length and one byte per record (its kai_op kind, ST_REC_WIDE: the chip-wide kernels may undo / commit it);
+    // its own device memory (stamps and verdict: sized at kai_stmt_begin, so that it does not grow while the Statement is open), the committed operations' device buffer and
+    // pinned staging (grown by the commit)
+    bool st_open = false; std::vector<uint8_t> st_rec; HandleBuf st_pin{true}, st_dev{false}, st_out{false}; size_t st_pod_cap = 0;
+    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &st_pin, &st_dev, &st_out, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &sn_pin, &sn_dev, &sn_out, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
 };
 
 // leave the function with a step's status unless it is KAI_OK; a HIP call's error becomes KAI_ERR_HIP with the call's text in kai_last_error
@@ -234,7 +239,7 @@ void free_session(kai_core* core, bool release = false) {
     if (release) { for (auto& sp : core->spare) (void)hipFree(sp.first); core->spare.clear(); }
     core->d_rank = nullptr; core->d_pkey = nullptr; core->d_remap = nullptr; core->remap_cap = 0; core->bt_alloc = false;
     core->allocs.clear(); core->sv_base = nullptr; core->xr_base = nullptr; core->mw_world = 0; core->rep_mem = nullptr; core->d_ctxs = nullptr; core->d_mw = nullptr; core->d_segs = nullptr; core->d_sg = nullptr;
-    core->open = false;
+    core->open = false; core->st_open = false;
 }
 // nothing leaves an entry point by an exception: the status and the message instead
 template <class F> int no_throw(kai_core* core, const std::string& what, F&& f) {

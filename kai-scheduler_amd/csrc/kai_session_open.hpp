@@ -168,7 +168,7 @@ int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     core->stats.upload_ms = ms;
     trim_spare(core);
     core->post_open_max = 0;  // (counted from here on: dalloc)
-    core->open = true; core->err = "ok";
+    core->open = true; core->st_open = false; core->err = "ok";
     return KAI_OK;
 }
 // the session's dynamic state from the HBM-resident snapshot: kai_session_reset, and kai_session_update after its scatter
@@ -181,7 +181,7 @@ int reset_state(kai_core* core) {
     if (c.P) { HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.p_status), core->d_status0, (size_t)c.P * 4, hipMemcpyDeviceToDevice, core->stream));
                HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.p_node), core->d_node0, (size_t)c.P * 4, hipMemcpyDeviceToDevice, core->stream)); }
     HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.q_share), core->d_shares0, (size_t)std::max(c.Q, 1) * 3 * sizeof(QShare), hipMemcpyDeviceToDevice, core->stream));
-    c.fast_ok = core->fast_ok0;
+    c.fast_ok = core->fast_ok0; core->st_open = false;  // (an open Statement goes with everything else the reset drops)
     if (c.P) HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.p_group), core->aux.group0, (size_t)c.P * 4, hipMemcpyDeviceToDevice, core->stream));
     HIP_TRY(core, hipMemcpyAsync(KAI_VP(c.next_new_group), &core->next_group0, 4, hipMemcpyHostToDevice, core->stream));
     { const size_t NG = (size_t)std::max(c.N, 1) * KAI_GMAX;

@@ -320,6 +320,7 @@ int session_update(kai_core* core, const kai_session_delta* d, const kai_session
     const int rc = no_throw(core, what, [&] { const int rca = check_update_args(core, d, r, what); return rca ? rca : update_impl(core, d ? d : &no_delta, r, wrote); });
     if (rc != KAI_OK && wrote) close_failed(core);  // the writes began: the session is no longer the snapshot it was, nor S' — closed, as a failed open leaves it
     else if (rc != KAI_OK && core->stream) (void)hipStreamSynchronize(core->stream);
+    if (rc == KAI_OK) core->st_open = false;  // the update drops an open Statement (kai_stmt.hpp) with the action results
     return rc;
 }
 }  // namespace

@@ -912,6 +912,109 @@ func ApplyOps(applied []AppliedOp) bool {
 	return true
 }
 
+// Statement is the device session's one open (uncommitted) Statement (kai_stmt_*, include/kai_core.h): what a Go-side allocate loop for a job the device cannot
+// place itself applies its operations to — Begin, per node set of SubsetNodes a Checkpoint, per task OrderedNodes and Apply, Rollback when the gang does not fit,
+// Commit or Discard at the end, as allocateSubGroupSet and attemptToAllocateJob use framework.Statement (actions/common/allocate.go).  Source only: nothing in
+// action.Execute below uses it.  While it is open the device's actions, ApplyOps and StaleGangEviction are refused (KAI_ERR_STATE).  Every method returns false
+// without a device session, with `fallback` set, for a task or node the snapshot does not know and for a refusal of the entry point; a refused Apply (an
+// operation whose precondition fails) leaves the Statement open with its log as it was, so the caller may roll back and go on.
+type Statement struct {
+	pack   *packedSnapshot
+	podOf  map[*pod_info.PodInfo]int
+	nodeOf map[*node_info.NodeInfo]int
+}
+
+// Begin: kai_stmt_begin on the current device session; nil when there is none or a Statement is open already.
+func Begin() *Statement {
+	if current == nil || current.pack == nil || current.pack.fallback {
+		return nil
+	}
+	pack := current.pack
+	if rc := C.kai_stmt_begin(core, C.KAI_STMT_VERSION); rc != 0 {
+		return nil
+	}
+	s := &Statement{pack: pack, podOf: make(map[*pod_info.PodInfo]int, len(pack.pods)), nodeOf: make(map[*node_info.NodeInfo]int, len(pack.nodes))}
+	for i, t := range pack.pods {
+		s.podOf[t] = i
+	}
+	for i, n := range pack.nodes {
+		s.nodeOf[n] = i
+	}
+	return s
+}
+
+// Apply: kai_stmt_apply — the operations applied without the commit (an allocated task is left Allocated) and appended to the log.  Stmt of AppliedOp is not read.
+func (s *Statement) Apply(applied []AppliedOp) bool {
+	if s == nil || current == nil || s.pack != current.pack || s.pack.fallback {
+		return false
+	}
+	if len(applied) == 0 {
+		return true
+	}
+	ops := make([]C.kai_op, len(applied))
+	for i, a := range applied {
+		p, knownPod := s.podOf[a.Task]
+		n, knownNode := s.nodeOf[a.Node]
+		if !knownPod || !knownNode {
+			return false
+		}
+		ops[i].seq = C.int64_t(i)
+		ops[i].kind = C.int32_t(a.Kind)
+		ops[i].pod = C.int32_t(p)
+		ops[i].node = C.int32_t(n)
+		ops[i].job = -1
+	}
+	var res C.kai_stmt_result
+	return C.kai_stmt_apply(core, &ops[0], C.int64_t(len(ops)), 0, &res) == 0
+}
+
+// Checkpoint: kai_stmt_checkpoint — the log's length (no device call); -1 on a refusal.
+func (s *Statement) Checkpoint() int64 {
+	var cp C.int64_t
+	if s == nil || current == nil || s.pack != current.pack || C.kai_stmt_checkpoint(core, &cp) != 0 {
+		return -1
+	}
+	return int64(cp)
+}
+
+// Rollback: kai_stmt_rollback — the operations behind the checkpoint undone, last first.
+func (s *Statement) Rollback(cp int64) bool {
+	var res C.kai_stmt_result
+	return s != nil && current != nil && s.pack == current.pack && C.kai_stmt_rollback(core, C.int64_t(cp), 0, &res) == 0
+}
+
+// Discard: kai_stmt_discard — every operation undone, the Statement closed.
+func (s *Statement) Discard() bool {
+	var res C.kai_stmt_result
+	return s != nil && current != nil && s.pack == current.pack && C.kai_stmt_discard(core, 0, &res) == 0
+}
+
+// Commit: kai_stmt_commit — the surviving operations committed on the device (allocated tasks become Binding) and handed back in log order, for the caller to replay
+// into the live session as action.Execute replays an action's; the Statement is closed.  A device fault sets `fallback`.
+func (s *Statement) Commit() ([]AppliedOp, bool) {
+	if s == nil || current == nil || s.pack != current.pack || s.pack.fallback {
+		return nil, false
+	}
+	n := s.Checkpoint()
+	if n < 0 {
+		return nil, false
+	}
+	ops := make([]C.kai_op, n+1)
+	var got C.int64_t
+	var res C.kai_stmt_result
+	if rc := C.kai_stmt_commit(core, &ops[0], C.int64_t(n), &got, &res); rc != 0 {
+		if rc == C.KAI_ERR_DEVICE_FAULT {
+			s.pack.fallback = true
+		}
+		return nil, false
+	}
+	out := make([]AppliedOp, int(got))
+	for i := range out {
+		out[i] = AppliedOp{Kind: int32(ops[i].kind), Task: s.pack.pods[int(ops[i].pod)], Node: s.pack.nodes[int(ops[i].node)]}
+	}
+	return out, true
+}
+
 // StaleGangEviction: the stalegangeviction action (actions/stalegangeviction/stalegangeviction.go:29-90) decided by the device against ITS session state — where
 // the placement actions of this cycle left it — in ONE kai_stale_gang_eviction call.  StalenessInfo.TimeStamp of every job goes down as nanoseconds (0 = nil), the
 // clock is the handle's (kai_core_set_now; OnSessionOpen sets it from Now), gracePeriod is ssn.GetGlobalDefaultStalenessGracePeriod() (negative: never evict).
