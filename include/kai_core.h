@@ -780,6 +780,60 @@ int kai_ordered_nodes_scored(kai_core* core, const kai_scored_query* queries, in
                              const kai_topo_score_row* score_rows, const uint8_t* deciles, int32_t n_score_rows,
                              int32_t k, kai_node_answer* out /* [n_queries][k] */, int32_t* n_out /* [n_queries] */);
 
+/* replaces: the innermost part of the allocate loop (actions/common/allocate.go:83-107 allocatePodSet with allocateTasksOnNodeSet inside) for gangs a caller places
+ * itself: per gang the loop over its node sets, per set the chain of its tasks' placements, inside the open Statement and over the Statement's own log — ONE call for
+ * many gangs instead of two calls (kai_ordered_nodes with k = 1, kai_stmt_apply of one operation) per task.  The sets come from kai_subset_nodes(_scored); the call is
+ * allocatePodSet without its SubsetNodesFn.  It is indistinguishable from this loop over the existing calls, on the same handle in the same state:
+ *
+ *   for g in gangs, in array order:
+ *       cp = kai_stmt_checkpoint()
+ *       for s in sets[g.first_set .. g.first_set + g.n_sets), in order:
+ *           for t in tasks[g.first_task .. g.first_task + g.n_tasks), in order:
+ *               a = kai_ordered_nodes_scored(k = 1, {pod t, nodeset s, flags & KAI_PLACE_PIPELINE_ONLY, scores g.scores})     at the state reached
+ *               if a is empty: fail_at[s] = index of t in the gang; kai_stmt_rollback(cp); try the next set
+ *               kai_stmt_apply({a.is_pipeline ? KAI_OP_PIPELINE : KAI_OP_ALLOCATE, t, a.node})
+ *           if every task was placed: fail_at[s] = n_tasks; status KAI_PLACE_PLACED, set = position of s in the gang's list; go to the next gang
+ *       status KAI_PLACE_NO_FIT: its operations are gone, the gangs before it keep theirs, the next gang goes on
+ *
+ * — kai_pod_states, kai_node_states and kai_queue_shares bit for bit, the answers of every query call, the log, and everything a later kai_stmt_rollback (on either of
+ * its paths, to any checkpoint, the caller's earlier ones included), discard, commit or action gives.  The Statement stays open; only the call's own operations are
+ * rolled back, so a caller's outer checkpoint (a sub-group tree) still works.
+ * Outputs: answers_out[g]: status, set (-1: none), sets_tried, and first_op / n_ops: the gang's surviving operations in ops_out.  fail_at_out (may be NULL) is indexed
+ * like `sets`: the gang index of the first task the set had no node for (handleFailedTaskAllocation's numSchedulableTasks), n_tasks for the set that took the gang, -1
+ * for an entry that was not tried.  ops_out: the call's surviving operations in log order — kind, pod, node (the caller's index), job, seq = the position in the log,
+ * stmt 0; *n_ops (may be NULL) their number.  result (may be NULL): log_len after the call; path: KAI_APPLY_PATH_WIDE where the session qualifies for the chip-wide
+ * kernels (the records are then undone and committed by them), KAI_APPLY_PATH_ENGINE where the placing lane went through the engine's own Statement functions
+ * (KAI_APPLY_ENGINE_PATH: also where the chip-wide path qualifies).  The node search is the same in both.
+ * Refusals, all decided before the first write; the Statement stays open with its log as it was:
+ *  - what every kai_stmt_* call refuses (no session, no open Statement: KAI_ERR_STATE; a sharded handle, shared-GPU requests: KAI_ERR_UNSUPPORTED);
+ *  - KAI_ERR_INVALID_ARG: a wrong version, unknown flags, non-zero pad, a negative count, a NULL array with a count above 0, a gang's range outside tasks / sets, a gang
+ *    with n_tasks < 1 or n_sets < 1, a pod, set row or score row out of range, what kai_ordered_nodes_scored refuses in score rows and deciles, a pod named twice in tasks, an entry of tasks that two gangs share;
+ *  - KAI_ERR_STATE with result->first_bad = the index in `tasks` of the first pod that is not Pending at entry (decided by the first launch);
+ *  - KAI_ERR_CAPACITY: the log's length plus n_tasks above its room (2 n_pods + 32), ops_cap below n_tasks, or the sum of n_tasks x n_sets over the gangs above 2^20
+ *    (one workgroup walks the chain: its running time is bounded by that sum times the size of a set).
+ * n_gangs == 0: KAI_OK without a device call.  Of nodeset_bitmaps only the rows that `sets` names are read and uploaded.  One staging upload, two launches (k_sp_prep chip-wide: the Pending check, every named set row compacted into an
+ * ascending name-rank list, so that a task's scan costs the set's size and not n_nodes; k_sp_place: one workgroup), one download, one synchronise. */
+#define KAI_PLACE_VERSION 1u
+#define KAI_PLACE_PIPELINE_ONLY 0x4u       /* isPipelineOnly for every task of the call; beside KAI_APPLY_ENGINE_PATH */
+enum { KAI_PLACE_PLACED = 0, KAI_PLACE_NO_FIT = 1 };
+typedef struct kai_place_params { uint32_t version; uint32_t flags; } kai_place_params;
+typedef struct kai_place_gang   { int32_t first_task, n_tasks;   /* tasks[first_task ..): pod indices, in the order they are placed */
+                                  int32_t first_set,  n_sets;    /* sets[first_set ..): rows of nodeset_bitmaps in the order they are tried, -1 = all nodes */
+                                  int32_t scores;                /* row of score_rows / deciles (kai_ordered_nodes_scored), -1 = none */
+                                  int32_t pad; } kai_place_gang;
+typedef struct kai_place_answer { int32_t status; int32_t set;   /* index in the gang's own list of the set that took it, -1 */
+                                  int32_t sets_tried; int32_t pad;
+                                  int64_t first_op; int64_t n_ops; /* its surviving operations in ops_out */ } kai_place_answer;
+int kai_stmt_place(kai_core* core, const kai_place_params* params,
+                   const kai_place_gang* gangs, int32_t n_gangs,
+                   const int32_t* tasks, int32_t n_tasks, const int32_t* sets, int32_t n_sets,
+                   const uint32_t* nodeset_bitmaps, int32_t n_nodesets,
+                   const kai_topo_score_row* score_rows, const uint8_t* deciles, int32_t n_score_rows,
+                   kai_place_answer* answers_out /* [n_gangs] */,
+                   int32_t* fail_at_out /* [n_sets] or NULL */,
+                   kai_op* ops_out, int64_t ops_cap, int64_t* n_ops /* may be NULL */,
+                   kai_stmt_result* result /* may be NULL */);
+
 /* session-state read-back (what the shim mirrors into PodInfo.Status/NodeName and NodeInfo.Idle/Releasing) */
 int kai_pod_states(kai_core* core, int32_t* status_out, int32_t* node_out, int cap);
 int kai_node_states(kai_core* core, kai_node_state* out, int cap);

@@ -245,6 +245,26 @@ class KaiStmtResult(C.Structure):
     _fields_ = [("first_bad", C.c_int64), ("log_len", C.c_int64), ("path", C.c_int32), ("pad", C.c_int32)]
 
 
+PLACE_VERSION, PLACE_PIPELINE_ONLY = 1, 0x4  # KAI_PLACE_VERSION, KAI_PLACE_PIPELINE_ONLY (beside APPLY_ENGINE_PATH)
+PLACE_PLACED, PLACE_NO_FIT = 0, 1            # kai_place_answer.status
+
+
+class KaiPlaceParams(C.Structure):
+    """kai_place_params (include/kai_core.h): kai_stmt_place's flags."""
+    _fields_ = [("version", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KaiPlaceGang(C.Structure):
+    """kai_place_gang: a gang's tasks (a range of the call's pod list, in placement order), its node sets (a range of the call's set list, in the order they are tried;
+    an entry is a row of the node-set bitmaps or -1 = all nodes) and its row of the score rows / deciles (-1 = none)."""
+    _fields_ = [("first_task", C.c_int32), ("n_tasks", C.c_int32), ("first_set", C.c_int32), ("n_sets", C.c_int32), ("scores", C.c_int32), ("pad", C.c_int32)]
+
+
+class KaiPlaceAnswer(C.Structure):
+    """kai_place_answer: status (PLACE_*), the set of the gang's own list that took it (-1), the sets tried, and its surviving operations in the call's ops."""
+    _fields_ = [("status", C.c_int32), ("set", C.c_int32), ("sets_tried", C.c_int32), ("pad", C.c_int32), ("first_op", C.c_int64), ("n_ops", C.c_int64)]
+
+
 STALE_VERSION, STALE_DRY_RUN = 1, 0x1  # KAI_STALE_VERSION, KAI_STALE_DRY_RUN
 
 

@@ -21,7 +21,7 @@ from . import abi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KAI_CORE_LIB") or os.path.join(_HERE, "csrc", "libkai_core.so")  # KAI_CORE_LIB: another BUILD of the same HIP library (profiling variants)
 
-EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stmt_begin", "kai_stmt_apply", "kai_stmt_checkpoint", "kai_stmt_rollback", "kai_stmt_discard", "kai_stmt_commit", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes", "kai_subset_nodes_scored", "kai_ordered_nodes_scored",
+EXPORTS = ["kai_core_create", "kai_core_destroy", "kai_session_open", "kai_queue_shares", "kai_action_execute", "kai_best_node", "kai_best_nodes", "kai_ordered_nodes", "kai_ops_apply", "kai_stmt_begin", "kai_stmt_apply", "kai_stmt_checkpoint", "kai_stmt_rollback", "kai_stmt_discard", "kai_stmt_commit", "kai_stmt_place", "kai_stale_gang_eviction", "kai_job_order", "kai_subset_nodes", "kai_subset_nodes_scored", "kai_ordered_nodes_scored",
            "kai_pod_states", "kai_node_states", "kai_pod_gpu_groups", "kai_shard_attach", "kai_shard_attach_host", "kai_shard_rccl_id", "kai_shard_attach_rccl", "kai_shard_allgather_probe", "kai_action_stats_get", "kai_session_reset", "kai_session_update", "kai_session_update_rows", "kai_core_set_now", "kai_session_close", "kai_last_error", "kai_version"]
 
 
@@ -133,6 +133,9 @@ def load_library(path: str = LIB_PATH):
     lib.kai_stmt_rollback.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(abi.KaiStmtResult)]
     lib.kai_stmt_discard.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(abi.KaiStmtResult)]
     lib.kai_stmt_commit.argtypes = [C.c_void_p, C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64), C.POINTER(abi.KaiStmtResult)]
+    lib.kai_stmt_place.argtypes = [C.c_void_p, C.POINTER(abi.KaiPlaceParams), C.POINTER(abi.KaiPlaceGang), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                   C.POINTER(C.c_uint32), C.c_int32, C.POINTER(abi.KaiTopoScoreRow), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(abi.KaiPlaceAnswer), C.POINTER(C.c_int32),
+                                   C.POINTER(abi.KaiOp), C.c_int64, C.POINTER(C.c_int64), C.POINTER(abi.KaiStmtResult)]
     lib.kai_stale_gang_eviction.argtypes = [C.c_void_p, C.POINTER(abi.KaiStaleParams), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(abi.KaiOp), C.c_int64,
                                             C.POINTER(C.c_int64), C.POINTER(abi.KaiStaleResult)]
     lib.kai_job_order.argtypes = [C.c_void_p, C.POINTER(abi.KaiJobOrderParams), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -602,6 +605,40 @@ class Statement:
         self.open = self.open and rc != 0
         self._done(rc, res)
         return ops[:n.value].copy(), res
+
+    def place(self, gangs, nodesets=None, score_rows=None, deciles=None, pipeline_only: bool = False, engine_path: bool = False):
+        """kai_stmt_place: whole gangs placed on their node sets in one call — per gang a checkpoint, its sets in order, per set its tasks in order, each on the best
+        node of the set at the state its predecessors left; a set without a node for a task is rolled back and the next one is tried.
+        gangs: (pods, sets) or (pods, sets, scores) per gang — pods in placement order, sets as indices into `nodesets` in the order they are tried (-1 / None = all
+        nodes), scores a row of score_rows / deciles (subset_nodes_scored's outputs) or -1; nodesets: node sets as index lists or boolean masks (a row of subset_nodes'
+        masks as it is).  Returns (answers, fail_at, ops, result): the kai_place_answer records; per gang an int32 array over its sets — the gang's index of the first
+        task the set had no node for, len(pods) for the set that took it, -1 for a set that was not tried; the call's surviving operations as kai_op records (log order,
+        seq = the position in the log); the kai_stmt_result.  A refusal raises KaiError with the result as its `.result` and leaves the Statement open as it was."""
+        _q, words, n_rows = self.ssn._node_queries(np.zeros(0, np.int32), nodesets, None, None)
+        G = len(gangs)
+        gv = np.zeros(max(G, 1), dtype=np.dtype([("first_task", "<i4"), ("n_tasks", "<i4"), ("first_set", "<i4"), ("n_sets", "<i4"), ("scores", "<i4"), ("pad", "<i4")]))  # kai_place_gang
+        tasks, sets = [], []
+        for g, gang in enumerate(gangs):
+            pods, ss = list(np.asarray(gang[0], dtype=np.int64).ravel()), [-1 if s is None else int(s) for s in np.asarray(gang[1], dtype=object).ravel()]
+            gv[g] = (len(tasks), len(pods), len(sets), len(ss), int(gang[2]) if len(gang) > 2 and gang[2] is not None else -1, 0)
+            tasks += pods; sets += ss
+        tv, sv = np.array(tasks + [0], np.int32), np.array(sets + [0], np.int32)
+        T, S = len(tasks), len(sets)
+        n_sr = 0 if score_rows is None else len(score_rows)
+        sr = np.ascontiguousarray(score_rows, dtype=_SCORE_ROW_DTYPE) if n_sr else None
+        dc = np.ascontiguousarray(deciles, dtype=np.uint8) if n_sr else None
+        ans = np.zeros(max(G, 1), dtype=np.dtype([("status", "<i4"), ("set", "<i4"), ("sets_tried", "<i4"), ("pad", "<i4"), ("first_op", "<i8"), ("n_ops", "<i8")]))  # kai_place_answer
+        fail = np.full(max(S, 1), -1, np.int32)
+        ops = np.zeros(max(T, 1), _OP_DTYPE)
+        n, res = C.c_int64(0), abi.KaiStmtResult()
+        params = abi.KaiPlaceParams(abi.PLACE_VERSION, (abi.PLACE_PIPELINE_ONLY if pipeline_only else 0) | (abi.APPLY_ENGINE_PATH if engine_path else 0))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self.core.lib.kai_stmt_place(self.core.handle, C.byref(params), gv.ctypes.data_as(C.POINTER(abi.KaiPlaceGang)), G, ip(tv), T, ip(sv), S,
+                                          words.ctypes.data_as(C.POINTER(C.c_uint32)) if n_rows else None, n_rows,
+                                          sr.ctypes.data_as(C.POINTER(abi.KaiTopoScoreRow)) if n_sr else None, dc.ctypes.data_as(C.POINTER(C.c_uint8)) if n_sr else None, n_sr,
+                                          ans.ctypes.data_as(C.POINTER(abi.KaiPlaceAnswer)), ip(fail), ops.ctypes.data_as(C.POINTER(abi.KaiOp)), T, C.byref(n), C.byref(res))
+        self._done(rc, res)
+        return ans[:G], [fail[gv["first_set"][g]: gv["first_set"][g] + gv["n_sets"][g]].copy() for g in range(G)], ops[:n.value].copy(), res
 
     def __enter__(self):
         return self

@@ -599,6 +599,135 @@ int kai_stmt_commit(kai_core* core, kai_op* ops_out, int64_t ops_cap, int64_t* n
     return KAI_OK;
 }
 
+int kai_stmt_place(kai_core* core, const kai_place_params* params, const kai_place_gang* gangs, int32_t n_gangs, const int32_t* tasks, int32_t n_tasks, const int32_t* sets, int32_t n_sets,
+                   const uint32_t* nodeset_bitmaps, int32_t n_nodesets, const kai_topo_score_row* score_rows, const uint8_t* deciles, int32_t n_score_rows,
+                   kai_place_answer* answers_out, int32_t* fail_at_out, kai_op* ops_out, int64_t ops_cap, int64_t* n_ops, kai_stmt_result* result) {
+    // every host-decidable refusal before the first device call; `result` always leaves with a defined content, the outputs are written only after the answers came back
+    KAI_TRY(st_entry(core, "kai_stmt_place", true, result));
+    auto no = [&](int code, const char* why) { core->err = std::string("kai_stmt_place: ") + why; return code; };
+    if (!params || params->version != KAI_PLACE_VERSION) return no(KAI_ERR_INVALID_ARG, "NULL params or a wrong version");
+    if (params->flags & ~(KAI_APPLY_ENGINE_PATH | KAI_PLACE_PIPELINE_ONLY)) return no(KAI_ERR_INVALID_ARG, "unknown flag bits");
+    if (n_gangs < 0 || n_tasks < 0 || n_sets < 0 || n_nodesets < 0 || n_score_rows < 0 || ops_cap < 0) return no(KAI_ERR_INVALID_ARG, "a negative count or capacity");
+    if ((n_gangs > 0 && (!gangs || !answers_out)) || (n_tasks > 0 && (!tasks || !ops_out)) || (n_sets > 0 && !sets) || (n_nodesets > 0 && !nodeset_bitmaps) || (n_score_rows > 0 && (!score_rows || !deciles)))
+        return no(KAI_ERR_INVALID_ARG, "a NULL array with a count above 0");
+    KaiCtx& c = core->ctx;
+    const int N = c.N, P = c.P, D = c.D, TL = c.TL, W = (N + 31) / 32, G = n_gangs, T = n_tasks, S = n_sets, R = n_nodesets;
+    int64_t work = 0;
+    std::vector<uint8_t> covered((size_t)T, 0);  // a task belongs to one gang: a pod placed by one gang is no longer Pending for the next
+    for (int g = 0; g < G; g++) {
+        const kai_place_gang& x = gangs[g];
+        if (x.pad != 0) return no(KAI_ERR_INVALID_ARG, "pad is not zero");
+        if (x.n_tasks < 1 || x.n_sets < 1) return no(KAI_ERR_INVALID_ARG, "a gang with n_tasks < 1 or n_sets < 1");
+        if (x.first_task < 0 || (int64_t)x.first_task + x.n_tasks > T || x.first_set < 0 || (int64_t)x.first_set + x.n_sets > S) return no(KAI_ERR_INVALID_ARG, "a gang's range lies outside tasks / sets");
+        if (x.scores < -1 || x.scores >= n_score_rows) return no(KAI_ERR_INVALID_ARG, "scores outside -1 .. n_score_rows-1");
+        for (int i = 0; i < x.n_tasks; i++) { uint8_t& seen = covered[(size_t)x.first_task + i]; if (seen) return no(KAI_ERR_INVALID_ARG, "two gangs share an entry of tasks"); seen = 1; }
+        work += (int64_t)x.n_tasks * x.n_sets;
+    }
+    for (int i = 0; i < T; i++) if (tasks[i] < 0 || tasks[i] >= P) return no(KAI_ERR_INVALID_ARG, "pod index out of range");
+    for (int i = 0; i < S; i++) if (sets[i] < -1 || sets[i] >= R) return no(KAI_ERR_INVALID_ARG, "a set row outside -1 .. n_nodesets-1");
+    for (int s = 0; s < n_score_rows; s++) {  // what kai_ordered_nodes_scored refuses in the rows
+        if (score_rows[s].level_row < KAI_TOPO_SCORES_EMPTY || score_rows[s].level_row >= TL) return no(KAI_ERR_INVALID_ARG, "a level_row outside -2 .. n_topo_levels-1");
+        const uint8_t* row = deciles + (size_t)s * D;
+        for (int d = 0; d < D; d++) if (row[d] > 10 && row[d] != KAI_TOPO_NO_SCORE) return no(KAI_ERR_INVALID_ARG, "a decile that is neither <= 10 nor 255");
+    }
+    {   std::vector<int32_t> sorted(tasks, tasks + T); std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return no(KAI_ERR_INVALID_ARG, "a pod is named twice in tasks"); }
+    const int64_t len0 = (int64_t)core->st_rec.size();
+    if (len0 + T > (int64_t)st_log_room(c)) return no(KAI_ERR_CAPACITY, "the log would exceed its room (ops_cap / 2 = 2 n_pods + 32 records)");
+    if (ops_cap < T) return no(KAI_ERR_CAPACITY, "ops_cap is below n_tasks");
+    if (work > KAI_SP_MAX_WORK) return no(KAI_ERR_CAPACITY, "the sum of n_tasks x n_sets over the gangs is above 2^20 (one workgroup walks the chain)");
+    if ((int64_t)n_score_rows * (D + 8) > ((int64_t)1 << 30)) return no(KAI_ERR_CAPACITY, "n_score_rows x (n_domains + 8) above 2^30");
+    if (n_ops) *n_ops = 0;
+    if (G == 0) return KAI_OK;
+    // ---- the rows the sets name and their sizes: a popcount of the caller's words over the N nodes (what k_sp_prep writes per row)
+    std::vector<int32_t> row_off((size_t)R + 1, 0), used;
+    for (int i = 0; i < S; i++) if (sets[i] >= 0 && !row_off[(size_t)sets[i] + 1]) { row_off[(size_t)sets[i] + 1] = 1; used.push_back(sets[i]); }
+    int64_t list_len = 0;
+    {   const uint32_t last = (N & 31) ? ((1u << (N & 31)) - 1u) : 0xffffffffu;
+        std::vector<int32_t> size((size_t)R, 0);
+        parallel_chunks(used.size(), [&](int, size_t i0, size_t i1) { for (size_t i = i0; i < i1; i++) {
+            const uint32_t* row = nodeset_bitmaps + (size_t)used[i] * W; int n = 0;
+            for (int w = 0; w < W; w++) n += __builtin_popcount(w == W - 1 ? row[w] & last : row[w]);
+            size[(size_t)used[i]] = n; } });
+        for (int r = 0; r < R; r++) { row_off[(size_t)r] = (int32_t)list_len; list_len += size[(size_t)r]; if (list_len > (int64_t)0x7fffffff - 64) return no(KAI_ERR_CAPACITY, "the named node sets hold more than 2^31 nodes"); }
+        row_off[(size_t)R] = (int32_t)list_len; }
+    HIP_TRY(core, hipSetDevice(core->device));
+    // ---- the handle's scratch and staging: grow on demand, no allocation once the handle is warm
+    const int n_used = (int)used.size();
+    const SpLayout L(N, G, T, S, R, W, n_used, n_score_rows, D, (size_t)list_len);
+    bool grew = false;
+    KAI_TRY(reserve(core, core->sp_dev, L.end, std::max<size_t>(L.end + L.end / 2, (size_t)1 << 16), &grew));
+    if (grew) core->sp_perm_ok = false;  // (the new scratch does not hold the permutation)
+    KAI_TRY(reserve(core, core->sp_pin, L.down_end, std::max<size_t>(L.down_end + L.down_end / 2, (size_t)1 << 16)));
+    const bool wide_ok = !(params->flags & KAI_APPLY_ENGINE_PATH) && oa_wide_session(c);
+    if (!wide_ok) { const int rcs = solver_ensure(core); if (rcs) return rcs; }  // (binds core->ctx.sv: the context is read after it; before the first write)
+    // ---- one staging upload, behind the permutation when the scratch does not hold this session's yet
+    unsigned char* h = core->sp_pin.p; unsigned char* d = core->sp_dev.p;
+    const size_t up0 = core->sp_perm_ok ? L.gangs : L.perm, up_end = L.head + sizeof(SpHead);
+    if (!core->sp_perm_ok && N > 0) std::memcpy(h + L.perm, core->perm.data(), (size_t)N * 4);
+    std::memcpy(h + L.gangs, gangs, (size_t)G * sizeof(kai_place_gang));
+    std::memcpy(h + L.tasks, tasks, (size_t)T * 4);
+    std::memcpy(h + L.sets, sets, (size_t)S * 4);
+    if (n_used) std::memcpy(h + L.used, used.data(), (size_t)n_used * 4);
+    std::memcpy(h + L.row_off, row_off.data(), ((size_t)R + 1) * 4);
+    for (int i = 0; i < n_used; i++) std::memcpy(h + L.rows_in + (size_t)i * W * 4, nodeset_bitmaps + (size_t)used[(size_t)i] * W, (size_t)W * 4);  // only the rows the sets name
+    if (n_score_rows) { std::memcpy(h + L.score_rows, score_rows, (size_t)n_score_rows * sizeof(kai_topo_score_row)); if (D > 0) std::memcpy(h + L.deciles, deciles, (size_t)n_score_rows * D); }
+    SpHead* hh = reinterpret_cast<SpHead*>(h + L.head); std::memset(hh, 0, sizeof(SpHead)); hh->bad = KAI_OA_NONE; hh->len = (int32_t)len0;
+    HIP_TRY(core, hipMemcpyAsync(d + up0, h + up0, up_end - up0, hipMemcpyHostToDevice, core->stream));
+    core->sp_perm_ok = true;
+    SpArgs a{};
+    a.G = G; a.T = T; a.S = S; a.R = R; a.W = W; a.n_used = n_used; a.len0 = (int32_t)len0; a.flags = params->flags & KAI_PLACE_PIPELINE_ONLY;
+    a.gangs = (KAI_GP(const kai_place_gang))(d + L.gangs); a.tasks = (KAI_GP(const int32_t))(d + L.tasks); a.sets = (KAI_GP(const int32_t))(d + L.sets);
+    a.rows_in = (KAI_GP(const uint32_t))(d + L.rows_in); a.perm = (KAI_GP(const int32_t))(d + L.perm); a.used_rows = (KAI_GP(const int32_t))(d + L.used);
+    a.row_off = (KAI_GP(const int32_t))(d + L.row_off); a.list = (KAI_GP(int32_t))(d + L.list);
+    a.score_rows = (KAI_GP(const kai_topo_score_row))(d + L.score_rows); a.deciles = (KAI_GP(const uint8_t))(d + L.deciles);
+    a.head = (KAI_GP(SpHead))(d + L.head); a.stamp = (KAI_GP(int32_t))(core->st_dev.p + StLayout(core->st_pod_cap).stamp);
+    a.answers = (KAI_GP(kai_place_answer))(d + L.answers); a.fail_at = (KAI_GP(int32_t))(d + L.fail_at); a.ops = (KAI_GP(kai_op))(d + L.ops);
+    // ---- two launches, one download, one synchronise
+    // (KAI_PLACE_PROF: every launch between two events and waited for, the milliseconds per kernel printed; tools/stmt_place_timing.py reads the line)
+    static const bool prof = std::getenv("KAI_PLACE_PROF") != nullptr;
+    float prof_ms[2] = {0, 0};
+    auto timed = [&](int k, auto&& launch) {
+        if (!prof) { launch(); return; }
+        (void)hipEventRecord(core->ev0, core->stream); launch(); (void)hipEventRecord(core->ev1, core->stream); (void)hipEventSynchronize(core->ev1);
+        float ms = 0; if (hipEventElapsedTime(&ms, core->ev0, core->ev1) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+        prof_ms[k] += ms;
+    };
+    const size_t prep_items = std::max<size_t>(std::max<size_t>((size_t)T, (size_t)S), (size_t)n_used * 64);
+    timed(0, [&] { hipLaunchKernelGGL(k_sp_prep, dim3((unsigned)((prep_items + KAI_BN_WG - 1) / KAI_BN_WG)), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a); });
+    if (wide_ok) timed(1, [&] { hipLaunchKernelGGL(k_sp_place, dim3(1), dim3(KAI_BN_WG), 0, core->stream, core->ctx, a); });
+    else timed(1, [&] { hipLaunchKernelGGL(k_sp_place_engine, dim3(1), dim3(64), 0, core->stream, core->ctx, a); });
+    SpHead hv{};
+    auto read_back = [&]() -> int {
+        HIP_TRY(core, hipGetLastError());
+        HIP_TRY(core, hipMemcpyAsync(h + L.head, d + L.head, L.down_end - L.head, hipMemcpyDeviceToHost, core->stream));
+        HIP_TRY(core, hipStreamSynchronize(core->stream));
+        std::memcpy(&hv, h + L.head, sizeof(SpHead));
+        return KAI_OK;
+    };
+    if (int rc = read_back()) return st_lost(core, rc);
+    if (prof) std::fprintf(stderr, "kai stmt place: path %d gangs %d | k_sp_prep %.4f k_sp_place %.4f ms\n", wide_ok ? KAI_APPLY_PATH_WIDE : KAI_APPLY_PATH_ENGINE, G, prof_ms[0], prof_ms[1]);
+    if (hv.bad != KAI_OA_NONE) {
+        if (result) result->first_bad = hv.bad;
+        return no(KAI_ERR_STATE, "a pod of tasks is not Pending (result->first_bad is its index in tasks)");
+    }
+    const bool wide = wide_ok;
+    if (hv.fault || (hv.applied && hv.applied != (wide ? KAI_APPLY_PATH_WIDE : KAI_APPLY_PATH_ENGINE)) || hv.len < len0 || hv.len > len0 + T) {
+        char buf[200]; std::snprintf(buf, sizeof buf, "kai_stmt_place: device engine fault code %d (engine source line %d), path reported %d; the Statement is closed", hv.fault, hv.fault_line, hv.applied);
+        core->err = buf; core->st_open = false; return KAI_ERR_DEVICE_FAULT;
+    }
+    const int64_t n = (int64_t)hv.len - len0;
+    std::memcpy(answers_out, h + L.answers, (size_t)G * sizeof(kai_place_answer));
+    if (fail_at_out && S > 0) std::memcpy(fail_at_out, h + L.fail_at, (size_t)S * 4);
+    {   const kai_op* src = reinterpret_cast<const kai_op*>(h + L.ops); const int32_t* perm = core->perm.data();  // name rank -> the caller's node index
+        const uint8_t mark = wide ? ST_REC_WIDE : 0;
+        for (int64_t i = 0; i < n; i++) { kai_op o = src[i]; o.node = perm[o.node]; ops_out[i] = o; core->st_rec.push_back((uint8_t)o.kind | mark); } }
+    if (n_ops) *n_ops = n;
+    if (hv.wrote) core->index_stale = true;  // neither mode keeps the class index: rebuilt before the next action reads it
+    if (result) { result->path = wide ? KAI_APPLY_PATH_WIDE : KAI_APPLY_PATH_ENGINE; result->log_len = (int64_t)core->st_rec.size(); }
+    return KAI_OK;
+}
+
 // kai_stale_gang_eviction's kernels for sg_drive (kai_stale_gangs.hpp), on top of the apply's launcher; pin: [the counts | the apply's verdict] in the handle's staging
 struct SgLauncher : OaLauncher {
     unsigned char* pin_counts;

@@ -26,6 +26,7 @@
 #include "kai_ordered_nodes.hpp"
 #include "kai_ops_apply.hpp"
 #include "kai_stmt.hpp"
+#include "kai_stmt_place.hpp"
 #include "kai_stale_gangs.hpp"
 #include "kai_job_order.hpp"
 #include "kai_subset_nodes.hpp"
@@ -120,7 +121,9 @@ struct kai_core {
     // its own device memory (stamps and verdict: sized at kai_stmt_begin, so that it does not grow while the Statement is open), the committed operations' device buffer and
     // pinned staging (grown by the commit)
     bool st_open = false; std::vector<uint8_t> st_rec; HandleBuf st_pin{true}, st_dev{false}, st_out{false}; size_t st_pod_cap = 0;
-    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &st_pin, &st_dev, &st_out, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &sn_pin, &sn_dev, &sn_out, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
+    // kai_stmt_place (kai_stmt_place.hpp): pinned staging and device scratch, grow, live with the handle; whether the scratch holds this session's permutation
+    HandleBuf sp_pin{true}, sp_dev{false}; bool sp_perm_ok = false;
+    std::vector<HandleBuf*> handle_bufs() { return {&rep_buf, &dl_pin, &dl_dev, &bn_pin, &bn_dev, &oa_pin, &oa_dev, &st_pin, &st_dev, &st_out, &sp_pin, &sp_dev, &sg_pin, &sg_dev, &jo_pin, &jo_dev, &sn_pin, &sn_dev, &sn_out, &pin_buf, &up_pin, &xpin, &xd_send, &xd_recv, &rpin}; }  // every one: kai_core_destroy
 };
 
 // leave the function with a step's status unless it is KAI_OK; a HIP call's error becomes KAI_ERR_HIP with the call's text in kai_last_error

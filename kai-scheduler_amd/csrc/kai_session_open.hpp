@@ -145,7 +145,7 @@ int session_open_impl(kai_core* core, const kai_snapshot_soa* s) {
     const auto t_prep = tnow();
     core->legacy_on = any_legacy_mig; core->legacy_cnt.clear();
     if (any_legacy_mig) flag_legacy_mig_nodes(s, prep, core->legacy_cnt);
-    core->perm = prep.perm; core->bn_perm_ok = false; core->oa_rank_ok = false; core->sn_tab_ok = false; core->sn_shape_ok = false;
+    core->perm = prep.perm; core->bn_perm_ok = false; core->sp_perm_ok = false; core->oa_rank_ok = false; core->sn_tab_ok = false; core->sn_shape_ok = false;
 
     // the context's arrays (kai_ctx_build.hpp; the order of its allocations is the session's layout in HBM), then what is the handle's own
     CtxBuildOut built;

@@ -136,6 +136,25 @@ KW_BODY void st_apply_body(const KaiCtx& c, const StArgs& s) {
     if (go && i == 0) { a.head->applied = KAI_APPLY_PATH_WIDE; c.st->ops_len = s.len + a.n; }
 }
 
+// one record undone (k_st_undo: a thread per record; k_sp_place: a lane per record of a set that failed).  false: an OP_UNDO record, nothing written
+KW_BODY bool st_undo_record(const KaiCtx& c, KAI_GP(int32_t) stamp, double* s_acc, int n_in, const StmtOp& op) {
+    const int p = op.pod;
+    if (op.name != OP_ALLOCATE && op.name != OP_PIPELINE && op.name != OP_EVICT) return false;
+    kw::atomic_add((int32_t*)&stamp[p], -1);
+    c.j_tta_valid[c.p_job[p]] = 0; c.p_virtual[p] = (uint8_t)op.prev_virtual;
+    if (op.name == OP_ALLOCATE) {  // Engine::unallocate
+        st_amounts(c, s_acc, n_in, KAI_OP_ALLOCATE, p, c.p_node[p], -1.0);
+        c.p_status[p] = KAI_POD_PENDING; c.p_node[p] = -1; c.p_on_node[p] = -1;
+    } else if (op.name == OP_PIPELINE) {  // Engine::unpipeline
+        st_amounts(c, s_acc, n_in, KAI_OP_PIPELINE, p, c.p_node[p], -1.0);
+        c.p_status[p] = op.prev_status; c.p_node[p] = op.prev_node; c.p_on_node[p] = -1;
+    } else {  // Engine::unevict: the node's copy is taken off and added again with the status that comes back
+        st_amounts(c, s_acc, n_in, KAI_OP_EVICT, p, op.prev_node, -1.0);
+        c.p_status[p] = op.prev_status; c.p_on_node_status[p] = op.prev_status;
+    }
+    return true;
+}
+
 KW_BODY void st_undo_body(const KaiCtx& c, const StArgs& s) {
     KW_SHARED double s_acc[KB_APPLY_INNER * 6];
     const OaArgs& a = s.a;
@@ -146,19 +165,7 @@ KW_BODY void st_undo_body(const KaiCtx& c, const StArgs& s) {
     kw::sync();
     if (i < s.len - s.cp) {
         const StmtOp op = c.ops[s.cp + i];
-        const int p = op.pod;
-        kw::atomic_add((int32_t*)&a.stamp[p], -1);
-        c.j_tta_valid[c.p_job[p]] = 0; c.p_virtual[p] = (uint8_t)op.prev_virtual;
-        if (op.name == OP_ALLOCATE) {  // Engine::unallocate
-            st_amounts(c, s_acc, n_in, KAI_OP_ALLOCATE, p, c.p_node[p], -1.0);
-            c.p_status[p] = KAI_POD_PENDING; c.p_node[p] = -1; c.p_on_node[p] = -1;
-        } else if (op.name == OP_PIPELINE) {  // Engine::unpipeline
-            st_amounts(c, s_acc, n_in, KAI_OP_PIPELINE, p, c.p_node[p], -1.0);
-            c.p_status[p] = op.prev_status; c.p_node[p] = op.prev_node; c.p_on_node[p] = -1;
-        } else if (op.name == OP_EVICT) {  // Engine::unevict: the node's copy is taken off and added again with the status that comes back
-            st_amounts(c, s_acc, n_in, KAI_OP_EVICT, p, op.prev_node, -1.0);
-            c.p_status[p] = op.prev_status; c.p_on_node_status[p] = op.prev_status;
-        } else { a.head->fault = FAULT_INTERNAL; a.head->fault_line = __LINE__; }  // (an OP_UNDO record: the host never sends such a range here)
+        if (!st_undo_record(c, a.stamp, s_acc, n_in, op)) { a.head->fault = FAULT_INTERNAL; a.head->fault_line = __LINE__; }  // (an OP_UNDO record: the host never sends such a range here)
     }
     kw::sync();
     st_flush_inner(c, s_acc, n_in);

@@ -968,6 +968,90 @@ func (s *Statement) Apply(applied []AppliedOp) bool {
 	return C.kai_stmt_apply(core, &ops[0], C.int64_t(len(ops)), 0, &res) == 0
 }
 
+// PlaceGang is one gang of Statement.Place: its tasks in the order they are placed, its node sets as indices into the call's bitmap rows in the order they are tried
+// (-1: all nodes), and its row of the call's score rows / deciles (-1: none).  PlacedGang is its answer: whether a set took it, which one (index in Sets, -1), the
+// sets tried, per tried set the index of the first task it had no node for (len(Tasks) for the set that took it, -1: not tried), and its operations.
+type PlaceGang struct {
+	Tasks  []*pod_info.PodInfo
+	Sets   []int32
+	Scores int32
+}
+type PlacedGang struct {
+	Placed    bool
+	Set       int32
+	SetsTried int32
+	FailAt    []int32
+	Ops       []AppliedOp
+}
+
+// Place: kai_stmt_place — whole gangs placed on their node sets in one call: per gang a checkpoint, its sets in order, per set its tasks in order, each on the best
+// node of the set at the state its predecessors left; a set without a node for a task is rolled back and the next one is tried (allocatePodSet's loop without its
+// SubsetNodesFn: bitmaps, scoreRows and deciles are SubsetNodes' outputs).  The Statement stays open; the operations are in its log.  A refusal (a task that is not
+// Pending, a task the snapshot does not know) leaves the Statement as it was and returns nil, false.
+func (s *Statement) Place(gangs []PlaceGang, bitmaps []uint32, nRows int, scoreRows []C.kai_topo_score_row, deciles []uint8, pipelineOnly bool) ([]PlacedGang, bool) {
+	if s == nil || current == nil || s.pack != current.pack || s.pack.fallback {
+		return nil, false
+	}
+	if len(gangs) == 0 {
+		return nil, true
+	}
+	gv := make([]C.kai_place_gang, len(gangs))
+	var tasks, sets []C.int32_t
+	for g, gang := range gangs {
+		gv[g] = C.kai_place_gang{first_task: C.int32_t(len(tasks)), n_tasks: C.int32_t(len(gang.Tasks)), first_set: C.int32_t(len(sets)), n_sets: C.int32_t(len(gang.Sets)), scores: C.int32_t(gang.Scores)}
+		for _, t := range gang.Tasks {
+			p, known := s.podOf[t]
+			if !known {
+				return nil, false
+			}
+			tasks = append(tasks, C.int32_t(p))
+		}
+		for _, r := range gang.Sets {
+			sets = append(sets, C.int32_t(r))
+		}
+	}
+	if len(tasks) == 0 || len(sets) == 0 {
+		return nil, false
+	}
+	params := C.kai_place_params{version: C.KAI_PLACE_VERSION}
+	if pipelineOnly {
+		params.flags = C.KAI_PLACE_PIPELINE_ONLY
+	}
+	answers := make([]C.kai_place_answer, len(gangs))
+	failAt := make([]C.int32_t, len(sets))
+	ops := make([]C.kai_op, len(tasks))
+	var rows *C.uint32_t
+	if nRows > 0 && len(bitmaps) > 0 {
+		rows = (*C.uint32_t)(unsafe.Pointer(&bitmaps[0]))
+	}
+	var sr *C.kai_topo_score_row
+	var dc *C.uint8_t
+	if len(scoreRows) > 0 && len(deciles) > 0 {
+		sr, dc = &scoreRows[0], (*C.uint8_t)(unsafe.Pointer(&deciles[0]))
+	}
+	var got C.int64_t
+	var res C.kai_stmt_result
+	if rc := C.kai_stmt_place(core, &params, &gv[0], C.int32_t(len(gv)), &tasks[0], C.int32_t(len(tasks)), &sets[0], C.int32_t(len(sets)), rows, C.int32_t(nRows),
+		sr, dc, C.int32_t(len(scoreRows)), &answers[0], &failAt[0], &ops[0], C.int64_t(len(ops)), &got, &res); rc != 0 {
+		if rc == C.KAI_ERR_DEVICE_FAULT {
+			s.pack.fallback = true
+		}
+		return nil, false
+	}
+	out := make([]PlacedGang, len(gangs))
+	for g := range out {
+		a := answers[g]
+		out[g] = PlacedGang{Placed: a.status == C.KAI_PLACE_PLACED, Set: int32(a.set), SetsTried: int32(a.sets_tried)}
+		for i := 0; i < int(gv[g].n_sets); i++ {
+			out[g].FailAt = append(out[g].FailAt, int32(failAt[int(gv[g].first_set)+i]))
+		}
+		for i := int(a.first_op); i < int(a.first_op+a.n_ops); i++ {
+			out[g].Ops = append(out[g].Ops, AppliedOp{Kind: int32(ops[i].kind), Task: s.pack.pods[int(ops[i].pod)], Node: s.pack.nodes[int(ops[i].node)]})
+		}
+	}
+	return out, true
+}
+
 // Checkpoint: kai_stmt_checkpoint — the log's length (no device call); -1 on a refusal.
 func (s *Statement) Checkpoint() int64 {
 	var cp C.int64_t
